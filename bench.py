@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """LM iterations/sec on a synthetic BAL Ladybug-1723-shaped problem (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One process per GPU (the driver launches N>1 with torch.distributed.run).  A
 "step" is ONE Levenberg-Marquardt iteration of the DENSE_SCHUR solve: LM
@@ -16,9 +16,14 @@ Multi-GPU (total work fixed => "strong"; the solver chooses, config.parallelism 
 camera sequence is cut into as many segments as pay (at most one per rank), rank r's device eliminates segment r and its
 points, the separators' block-tridiagonal system is all-reduced (a few MB) and factored by every rank; or SHARDED — points
 sharded, the reduced system (its blocks inside the envelope) all-reduced, Cholesky replicated; or REPLICATED when neither
-pays.  The same line carries the other configurations of BASELINE.json: one GPU — `c2` (BAL-49), `c4` (Venice-1778), `c5`
-(dense rows); several ranks — `venice` and `c5` (rows sharded), each with the distribution used, the bytes all-reduced per
-iteration and the milliseconds that takes; and on one GPU `predicted_multi_gpu`, the chain model's figures for 2, 4, 8.
+pays.
+
+A plain run sets up, warms up, times the K steps and prints the result line; `--dump-outputs DIR` also writes what the
+timed solve returns to its caller after its last step (dump_outputs).  `--full` adds what else this script measures: the
+CPU baseline (`cpu_baseline`), the untimed side runs (the SYRK alone, the full factorisation), and the other configurations
+of BASELINE.json: one GPU — `c2` (BAL-49), `c4` (Venice-1778), `c5` (dense rows); several ranks — `venice` and `c5` (rows
+sharded), each with the distribution used, the bytes all-reduced per iteration and the milliseconds that takes; and on one
+GPU `predicted_multi_gpu`, the chain model's figures for 2, 4, 8.
 
 stdout carries ONE line: the compact headline (at most 4 KB — metric, value, config, `roofline`, `cpu_baseline`), printed by
 rank 0 as soon as it is complete.  Everything else this run measures (the headline's detailed record and the other
@@ -70,6 +75,32 @@ def build_problem(sk, prob):
                      9 * prob.num_cameras + 3 * prob.point_index.astype(np.int64)], axis=1)
     problem.addResidualBlocks(sk.SnavelyReprojectionError.FUNCTOR_ID, prob.observations, loss, params, offs)
     return problem, params, loss
+
+
+DUMP_MAX_BYTES = 64 << 20
+ITERATION_FIELDS = ["cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease", "trust_region_radius",
+                    "step_is_valid", "step_is_successful"]
+
+
+def dump_outputs(out_dir, parameters, summary, warmup, steps):
+    """What the timed solve hands its caller after its last step, as float64 .npy files in `out_dir`: `parameters` (the
+    caller's parameter array, written back by sk_solver_finish), `final_cost`, and `timed_iterations` (one row per timed
+    step, columns ITERATION_FIELDS of the summary's log).  A parameter vector over the size cap is written as a fixed,
+    seeded sample (`parameters` at the indices in `parameters_index`)."""
+    os.makedirs(out_dir, exist_ok=True)
+    its = summary.iterations()[1 + warmup: 1 + warmup + steps]  # (log entry 0 is the initial point)
+    table = np.array([[it[k] for k in ITERATION_FIELDS] for it in its], dtype=np.float64).reshape(-1, len(ITERATION_FIELDS))
+    parameters = np.asarray(parameters, dtype=np.float64)
+    if parameters.nbytes + table.nbytes > DUMP_MAX_BYTES // 2:
+        n = DUMP_MAX_BYTES // 4 // 16  # (value + index, both float64, in a quarter of the cap)
+        index = np.sort(np.random.default_rng(SEED).choice(parameters.size, size=n, replace=False))
+        np.save(os.path.join(out_dir, "parameters_index.npy"), index.astype(np.float64))
+        parameters = parameters[index]
+    elif os.path.exists(os.path.join(out_dir, "parameters_index.npy")):
+        os.remove(os.path.join(out_dir, "parameters_index.npy"))  # (an earlier run's sample: not this run's output)
+    np.save(os.path.join(out_dir, "parameters.npy"), parameters)
+    np.save(os.path.join(out_dir, "final_cost.npy"), np.array([summary.finalCost()], dtype=np.float64))
+    np.save(os.path.join(out_dir, "timed_iterations.npy"), table)
 
 
 def pmc_traffic():
@@ -443,6 +474,11 @@ def main():
     ap.add_argument("--no-resident-kernels", action="store_true", help="sk_options_set_resident_kernels(o, 0): the same plans launch by launch (counter-collection passes)")
     ap.add_argument("--dissection", default="auto", choices=["auto", "on", "off"], help="(tuning) two-way dissection of the camera sequence on ONE device")
     ap.add_argument("--retained", default="auto", help="(tuning) retained points: auto, off, or a count (sk_options_set_retained_points(o, ON, count))")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: CPU baseline, untimed side runs, chain-model predictions, the other "
+                         "configurations of BASELINE.json (off: set-up, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed solve returns to its caller after its last step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -575,13 +611,15 @@ def main():
         solver_two_segments_us = 0.0
     summary = sk.Solver.Summary()
     solver.finish(summary)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, params.toArray(prob.parameters.size), summary, args.warmup, args.steps)
     # Untimed side measurement: the same kernel with the look-ahead off, i.e. alone on the chip.  In the
     # timed region above it shares the CUs with the panel chain of the next block-column group (and its
     # stream is masked off a few CUs per XCD), so its per-launch time there is longer by design.
     alone = None
     full_ms = None
     full_chol_s = None
-    if world == 1 and not args.no_lookahead and not args.no_alone:
+    if args.full and world == 1 and not args.no_lookahead and not args.no_alone:
         del solver
 
         def side_run(lookahead, envelope, nsteps=3):
@@ -698,7 +736,7 @@ def main():
         # segments, calibrated on this run: model(k) / model(1) x the measured Cholesky phase + the measured phases that
         # shard with the points / k (k segments).  UNMEASURED on more than one device until a SCALE run exists; printed so that one can be
         # read against it.
-        if world == 1 and model_us.get(1, 0.0) > 0.0:
+        if args.full and world == 1 and model_us.get(1, 0.0) > 0.0:
             ph = line["phases_ms_per_step"]
             shard = ph["jacobian_eval"] + ph["schur_assemble"] + ph["back_substitute"] + ph["cost_eval"]
             pred = {}
@@ -769,7 +807,7 @@ def main():
             # scaling without a collective).  Reported beside the headline, never in its place.
             line["independent_solves"] = {"value": world * args.steps / elapsed, "unit": "LM iterations/s over %d independent solves" % world, "scaling": "weak",
                                           "note": "the timed region of this run: each of the %d ranks completed its own solve of the whole problem, no collective" % world}
-        if args.cpu_iters > 0 and world == 1:
+        if args.full and args.cpu_iters > 0 and world == 1:
             line["cpu_baseline"] = cpu_baseline(prob, args.cpu_iters, envelope=not args.full_factorisation, full_iters=args.cpu_full_iters)
         elif world == 1:
             line["cpu_baseline"] = None
@@ -816,7 +854,7 @@ def main():
     # ---- the other configurations of BASELINE.json in the same run (every rank takes part; rank 0 reports).  None of them may
     # cost the headline its line: whatever goes wrong in one is recorded in its place. ----
     extra = {}
-    if not args.no_alone and args.workload == "ladybug-1723-156502":
+    if args.full and not args.no_alone and args.workload == "ladybug-1723-156502":
         try:
             del solver
         except NameError:

@@ -5,6 +5,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,3 +74,38 @@ def test_phases_are_those_of_the_timed_region():
     after = [1.1, 2.2, 3.6, 4.0, 5.05, 6.0]
     ph = bench.phases_per_step(before, after, 10)
     assert ph["cholesky"] == pytest.approx(60.0) and ph["jacobian_eval"] == pytest.approx(10.0) and ph["allreduce"] == 0.0
+
+
+class CannedSummary:
+    """The two accessors of sk.Solver.Summary that bench.dump_outputs reads: a log of 1 + warm-up + timed iterations."""
+
+    def __init__(self, n_logged):
+        self.log = [{k: float(100 * i + j) for j, k in enumerate(bench.ITERATION_FIELDS)} for i in range(n_logged)]
+
+    def iterations(self):
+        return self.log
+
+    def finalCost(self):
+        return 0.25
+
+
+def test_dump_outputs_holds_the_timed_steps_in_float64(tmp_path):
+    x = np.linspace(-1.0, 1.0, 1000)
+    bench.dump_outputs(str(tmp_path), x, CannedSummary(1 + 2 + 5), warmup=2, steps=5)
+    assert sorted(os.listdir(tmp_path)) == ["final_cost.npy", "parameters.npy", "timed_iterations.npy"]
+    p, c, t = (np.load(tmp_path / n) for n in ("parameters.npy", "final_cost.npy", "timed_iterations.npy"))
+    assert p.dtype == c.dtype == t.dtype == np.float64
+    assert np.array_equal(p, x) and c.tolist() == [0.25]
+    assert t.shape == (5, len(bench.ITERATION_FIELDS)) and t[0, 0] == 300.0 and t[-1, -1] == 700.0 + len(bench.ITERATION_FIELDS) - 1
+
+
+def test_dump_outputs_samples_a_large_parameter_vector_the_same_way_every_run(tmp_path, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 16)
+    x = np.arange(20000, dtype=np.float64) * 0.5
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), x, CannedSummary(4), warmup=1, steps=2)
+    idx = np.load(tmp_path / "a" / "parameters_index.npy")
+    p = np.load(tmp_path / "a" / "parameters.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "b" / "parameters_index.npy"))
+    assert np.array_equal(p, x[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The rocprofv3 evidence of a round, on the code as it stands: run on the GPU box from the repo root,
 #   bash tools/profile_round.sh r04 > gpurun_out/r04_profile.log 2>&1
-# writes under gpurun_out/ (copied to profiles/ afterwards): <tag>_bench.json (plain run), <tag>_bench_under_rocprof.json +
+# writes under $OUT (copied to profiles/ afterwards): <tag>_bench.json (bench.py --full, no profiler), <tag>_bench_under_rocprof.json +
 # <tag>_kernel_stats.csv + <tag>_syrk_timed_region.txt (one --kernel-trace --stats run), <tag>_pmc_traffic.json (separate FETCH_SIZE /
 # WRITE_SIZE passes) and <tag>_pmc_mfma.json (MFMA counters).  Counter passes run with --no-resident-kernels
 # (sk_options_set_resident_kernels(o, 0)): counter collection serialises the kernels of a process, and a resident kernel that
@@ -13,7 +13,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-SK_BENCH_DETAILS=$OUT/${TAG}_bench_details.json python3 $ROOT/bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+SK_BENCH_DETAILS=$OUT/${TAG}_bench_details.json python3 $ROOT/bench.py --steps 20 --warmup 5 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo "bench done"
 export SK_BENCH_DETAILS=$OUT/${TAG}_bench_under_rocprof_details.json
 rm -rf /tmp/prof_kt && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- python3 $ROOT/bench.py --steps 20 --warmup 5 --cpu-iters 0 --no-alone --no-c5 > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/${TAG}_rocprof.err
