@@ -202,6 +202,17 @@ class BalSolver : public SolverBase {
     if (name == "allreduce_bytes") { *value = (double)packed_elems_ * sizeof(double); return true; }
     if (name == "allreduce_bytes_full_triangle") { *value = (double)tri_packed_elems(nblk) * sizeof(double); return true; }
     if (name == "dissected") { *value = dissected_ ? 1.0 : 0.0; return true; }
+    if (name == "pair_segments_short") { *value = d_.num_short_segments; return true; }  // camera pairs of bal_pair_kernel / of bal_pair_long_kernel
+    if (name == "pair_segments_long") { *value = d_.num_long_segments; return true; }
+    if (name == "graph_replay") { *value = graph_mode_ ? 1.0 : 0.0; return true; }  // the iteration replays as one hipGraph (setup())
+    if (name == "host_callback_blocks" || name == "tape_blocks") {  // residual blocks evaluated by the caller's code / by a recorded tape
+      const bool host = name == "host_callback_blocks";
+      size_t c = 0;
+      for (size_t b = 0; b < problem_->rb_functor.size(); ++b)
+        c += host ? problem_->rb_functor[b] == SK_FUNCTOR_HOST_CALLBACK : problem_->tape_of_block(b) != nullptr;
+      *value = (double)c;
+      return true;
+    }
     if (name == "retained_points") { *value = (double)retained_pts_.size(); return true; }
     if (name == "retained_model_us") { *value = retained_model_us_; return true; }
     if (name == "retained_model_us_without") { *value = retained_without_us_; return true; }

@@ -34,6 +34,7 @@ class DenseRowsSolver : public SolverBase {
   bool stat(const std::string& name, double* value) const override {
     if (name == "allreduce_bytes") { *value = (double)b_pack_.n * sizeof(double); return true; }
     if (name == "jtj_flops_algorithmic") { *value = (double)m_ * (double)n_ * ((double)n_ + 1.0); return true; }
+    if (name == "gram_slabs") { *value = (double)nslabs_; return true; }  // parts of the K dimension of the Gram kernel (setup())
     return false;
   }
 

@@ -53,17 +53,21 @@ def main():
     prob = bal.generate(shape[0], shape[1], shape[2], seed=shape[3], revisits=[(60, 350, 12, 40), (200, 520, 12, 40)] if revisits else ())
     x_plain, s_plain = solve_bal_gpu(prob, **({"setCholeskyBorder": "off"} if revisits else ({"setRetainedPoints": "off"} if kept else {})))
     problem, params, loss = bal_problem_to_sk(prob)
-    options = sk.Solver.Options()
-    options.setLinearSolverType(sk.LinearSolverType.DENSE_SCHUR)
     hook = HostStagedAllReduce()
-    options.setDistributed(rank, world, hook)
-    options.setDistributionMode({"auto": 0, "sharded": 1, "replicated": 2, "segmented": 3}[mode])
-    if revisits:
-        options.setCholeskyBorder("on")
-    if kept:
-        options.setRetainedPoints("on", 12)
-    if kept2:
-        options.setMaxSegments(2)
+
+    def make_options():
+        options = sk.Solver.Options()
+        options.setLinearSolverType(sk.LinearSolverType.DENSE_SCHUR)
+        options.setDistributed(rank, world, hook)
+        options.setDistributionMode({"auto": 0, "sharded": 1, "replicated": 2, "segmented": 3}[mode])
+        if revisits:
+            options.setCholeskyBorder("on")
+        if kept:
+            options.setRetainedPoints("on", 12)
+        if kept2:
+            options.setMaxSegments(2)
+        return options
+    options = make_options()
     summary = sk.Solver.Summary()
     solver = sk.StepSolver(options, problem)
     used, t_allreduce, t_saved = solver.distribution()
@@ -113,6 +117,26 @@ def main():
     dist.all_reduce(hi, op=dist.ReduceOp.MAX)
     assert torch.equal(lo, hi)
     assert np.abs(x - x_plain).max() <= 1e-6 * max(1.0, np.abs(x_plain).max())
+    save = os.environ.get("STEP_CHECK_SAVE")
+    if save:
+        # tests/test_gpu_step_check.py: the same solve stopped after k = 1 .. STEP_CHECK_K iterations; rank 0 saves its x and log
+        import json
+        runs = []
+        for k in range(1, int(os.environ.get("STEP_CHECK_K", "2")) + 1):
+            problem_k, params_k, _ = bal_problem_to_sk(prob)
+            options_k = make_options()
+            options_k.setMaxNumIterations(k)
+            solver_k = sk.StepSolver(options_k, problem_k)
+            plan = {nm: solver_k.stat(nm) for nm in ("retained_points", "dissected", "segments")}
+            plan["distribution"] = solver_k.distribution()[0]
+            while not solver_k.step():
+                pass
+            summary_k = sk.Solver.Summary()
+            solver_k.finish(summary_k)
+            runs.append({"x": params_k.toArray(prob.num_parameters).tolist(), "log": summary_k.iterations(), "plan": plan})
+        if rank == 0:
+            with open(save, "w") as f:
+                json.dump({"world": world, "mode": mode, "runs": runs}, f)
     dist.barrier()
     if rank == 0:
         print("DIST_GPU2_OK world=%d mode=%s segments=%d calls=%d iterations=%d" % (world, mode, segments, hook.calls, summary.numIterations()))
