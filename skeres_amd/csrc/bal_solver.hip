@@ -213,6 +213,8 @@ class BalSolver : public SolverBase {
       *value = (double)c;
       return true;
     }
+    if (name == "tape_width") { *value = tape_mode_ ? bal_tape_width(tape_dev_.host) : 0; return true; }  // derivative slots per pass of the interpreter
+    if (name == "tape_lds_bytes") { *value = tape_mode_ ? (double)tape_lds_bytes(tape_dev_.host, bal_tape_width(tape_dev_.host), 256) : 0.0; return true; }
     if (name == "retained_points") { *value = (double)retained_pts_.size(); return true; }
     if (name == "retained_model_us") { *value = retained_model_us_; return true; }
     if (name == "retained_model_us_without") { *value = retained_without_us_; return true; }

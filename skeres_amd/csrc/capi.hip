@@ -349,8 +349,8 @@ int sk_cost_function_evaluate(const sk_cost_function* cf, double const* const* p
   if (sk_device_count() <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return -SK_ERR_NO_DEVICE; }
   const int nb = (int)c.block_sizes.size(), nres = c.num_residuals;
   std::vector<int> x_off(nb), j_off(nb);
-  int nx = 0, nj = 0; unsigned mask = 0;
-  for (int q = 0; q < nb; ++q) { x_off[q] = nx; nx += c.block_sizes[q]; j_off[q] = nj; nj += nres * c.block_sizes[q]; if (jacobians && jacobians[q]) mask |= 1u << q; }
+  int nx = 0, nj = 0; unsigned long long mask = 0;  // one bit per parameter block: a recorded functor has up to kTapeMaxDim = 64
+  for (int q = 0; q < nb; ++q) { x_off[q] = nx; nx += c.block_sizes[q]; j_off[q] = nj; nj += nres * c.block_sizes[q]; if (jacobians && jacobians[q]) mask |= 1ull << q; }
   std::vector<double> x(nx);
   for (int q = 0; q < nb; ++q) std::memcpy(&x[x_off[q]], parameters[q], c.block_sizes[q] * sizeof(double));
   DevBuf<double> dx, dc, dr, dj; DevBuf<int> dxo, djo, dok;
@@ -377,7 +377,7 @@ int sk_cost_function_evaluate(const sk_cost_function* cf, double const* const* p
 #undef SK_TRYN
   if (!ok) return 0;
   std::memcpy(residuals, r.data(), nres * sizeof(double));
-  for (int q = 0; q < nb; ++q) if ((mask >> q) & 1u) std::memcpy(jacobians[q], &j[j_off[q]], (size_t)nres * c.block_sizes[q] * sizeof(double));
+  for (int q = 0; q < nb; ++q) if ((mask >> q) & 1ull) std::memcpy(jacobians[q], &j[j_off[q]], (size_t)nres * c.block_sizes[q] * sizeof(double));
   return 1;
   SK_GUARD_END(-SK_ERR_INVALID_ARGUMENT)
 }

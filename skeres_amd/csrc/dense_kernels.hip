@@ -123,7 +123,7 @@ void launch_dense_sum(const double* v, int m, double* out, hipStream_t s) { hipL
 // (row-major kRes x N(q)) at jac + jac_off[q].
 template <class F>
 __global__ void single_eval_kernel(const double* consts, const double* x, const int* x_off, double* residuals, double* jac,
-                                   const int* jac_off, int want_jac, unsigned jac_mask, int* ok) {
+                                   const int* jac_off, int want_jac, unsigned long long jac_mask, int* ok) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   if (!want_jac) {
     const double* params[F::kBlocks];
@@ -150,7 +150,7 @@ __global__ void single_eval_kernel(const double* consts, const double* x, const 
   int off = 0;
   for (int q = 0; q < F::kBlocks; ++q) {
     const int nq = F::N(q);
-    if ((jac_mask >> q) & 1u) {
+    if ((jac_mask >> q) & 1ull) {
       int col = 0;
       for (int r = 0; r < F::kRes; ++r)
         for (int p = 0; p < nq; ++p) jac[jac_off[q] + col++] = out[r].v[off + p];
@@ -194,7 +194,7 @@ __global__ void dense_eval_tape_kernel(DenseEvalArgs a, TapeDev t) {
 // one residual block (sk_cost_function_evaluate); thread 0 of one wave
 template <int W>
 __global__ void single_eval_tape_kernel(TapeDev t, const double* consts, const double* x, const int* x_off, double* residuals, double* jac,
-                                        const int* jac_off, int want_jac, unsigned jac_mask, int* ok) {
+                                        const int* jac_off, int want_jac, unsigned long long jac_mask, int* ok) {
   extern __shared__ __attribute__((aligned(16))) double tape_lds[];
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   auto param = [&](int k) { return x[x_off[t.param_block[k]] + t.param_index[k]]; };
@@ -215,7 +215,7 @@ __global__ void single_eval_tape_kernel(TapeDev t, const double* consts, const d
     if (first == 0) for (int r = 0; r < t.num_residuals; ++r) residuals[r] = out[r].a;
     for (int w = 0; w < W && first + w < t.dim; ++w) {
       const int q = t.param_block[first + w], j = t.param_index[first + w];
-      if (!((jac_mask >> q) & 1u)) continue;
+      if (!((jac_mask >> q) & 1ull)) continue;
       int nq = 0;
       for (int k = 0; k < t.dim; ++k) nq += t.param_block[k] == q ? 1 : 0;
       for (int r = 0; r < t.num_residuals; ++r) jac[jac_off[q] + r * nq + j] = out[r].v[w];  // row-major num_residuals x N(q)
@@ -248,7 +248,7 @@ bool launch_dense_eval_tape(const TapeDevBuffers& tb, bool jac, const DenseEvalA
   }
 }
 bool launch_single_eval_tape(const TapeDevBuffers& tb, const double* consts, const double* x, const int* x_off, double* residuals, double* jac,
-                             const int* jac_off, int want_jac, unsigned jac_mask, int* ok, hipStream_t s) {
+                             const int* jac_off, int want_jac, unsigned long long jac_mask, int* ok, hipStream_t s) {
   const int threads = 64;
   const int W = tape_pick_width(tb.host, threads);
   if (W == 0) return false;
@@ -262,7 +262,7 @@ bool launch_single_eval_tape(const TapeDevBuffers& tb, const double* consts, con
 }
 
 void launch_single_eval(int functor_id, const double* consts, const double* x, const int* x_off, double* residuals, double* jac,
-                        const int* jac_off, int want_jac, unsigned jac_mask, int* ok, hipStream_t s) {
+                        const int* jac_off, int want_jac, unsigned long long jac_mask, int* ok, hipStream_t s) {
 #define SK_LAUNCH(F) hipLaunchKernelGGL((single_eval_kernel<F>), dim3(1), dim3(64), 0, s, consts, x, x_off, residuals, jac, jac_off, want_jac, jac_mask, ok)
   SK_DISPATCH_FUNCTOR(functor_id, SK_LAUNCH)
 #undef SK_LAUNCH

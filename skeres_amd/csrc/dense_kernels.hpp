@@ -43,9 +43,9 @@ void launch_dense_sum(const double* v, int m, double* out, hipStream_t s);
 // recorded functors (tape.hpp); false = the tape's register file does not fit the LDS (nothing was launched)
 bool launch_dense_eval_tape(const TapeDevBuffers& tb, bool jac, const DenseEvalArgs& a, hipStream_t s);
 bool launch_single_eval_tape(const TapeDevBuffers& tb, const double* consts, const double* x, const int* x_off, double* residuals, double* jac,
-                             const int* jac_off, int want_jac, unsigned jac_mask, int* ok, hipStream_t s);
+                             const int* jac_off, int want_jac, unsigned long long jac_mask, int* ok, hipStream_t s);
 void launch_single_eval(int functor_id, const double* consts, const double* x, const int* x_off, double* residuals, double* jac,
-                        const int* jac_off, int want_jac, unsigned jac_mask, int* ok, hipStream_t s);
+                        const int* jac_off, int want_jac, unsigned long long jac_mask, int* ok, hipStream_t s);
 void launch_dense_col_reduce(const double* J, const double* r, int m, int n, double* colsq, double* gs, hipStream_t s);
 struct ParamBlock;
 void launch_dense_project(const double* Jg, int m, int ng, const ParamBlock* blocks, int nblocks, const double* x, const double* scale, double* Jl, int nl,

@@ -32,6 +32,27 @@ class DenseSolver : public SolverBase {
     s->num_parameter_blocks = (int)problem_->block_size.size();
     s->num_parameters = ng_; s->num_residual_blocks = (int)problem_->rb_functor.size(); s->num_residuals = m_;
   }
+  bool stat(const std::string& name, double* value) const override {
+    // the interpreter's plan for the recorded functors: derivative slots per pass (the narrowest of the problem's tapes)
+    // and the dynamic LDS of its Jacobian kernel (the largest); 0 when the problem has no recorded functor
+    if (name == "tape_width" || name == "tape_lds_bytes") {
+      int width = 0; size_t lds = 0;
+      for (const auto& kv : tapes_dev_) {
+        const int W = tape_pick_width(kv.second.host, 128);
+        width = width == 0 ? W : std::min(width, W);
+        lds = std::max(lds, tape_lds_bytes(kv.second.host, W, 128));
+      }
+      *value = name == "tape_width" ? (double)width : (double)lds;
+      return true;
+    }
+    if (name == "tape_blocks") {  // residual blocks evaluated by a recorded tape
+      size_t c = 0;
+      for (const auto& kv : by_functor_) if (kv.first >= kTapeFunctorBase) c += kv.second.size();
+      *value = (double)c;
+      return true;
+    }
+    return false;
+  }
 
  private:
   int evaluate(const double* x_dev, bool jac);

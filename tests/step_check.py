@@ -202,6 +202,42 @@ class DenseRowsModel(_Model):
             yield r, [(J, np.zeros(len(c), dtype=np.int64))]
 
 
+class TapeModel(_Model):
+    """Residual blocks of recorded functors (skeres_amd/tape.py) evaluated by the long-double interpreter of tests/tape_reference.py
+    (run_np; neither device code nor the oracle, which has no tape interpreter).  groups: [(tape, parameter block sizes, captured
+    doubles [nb, ncap], offsets [nb, number of blocks] of each block's parameter blocks in x, loss spec or None)]; held: columns
+    of x that do not move (constant blocks, coordinates a subset parameterization holds); kind: as _Model's (default 0)."""
+
+    def __init__(self, n, groups, held=(), kind=None, chunk=4096):
+        self.n = int(n)
+        self.groups = groups
+        self.chunk = chunk
+        self.free = np.ones(self.n, dtype=bool)
+        self.free[np.asarray(list(held), dtype=np.int64)] = False
+        self.kind = np.zeros(self.n, dtype=np.int8) if kind is None else np.asarray(kind, dtype=np.int8)
+
+    def chunks(self, x):
+        from tape_reference import run_np
+        x = np.asarray(x, dtype=np.float64)
+        for tape, sizes, captured, offsets, loss in self.groups:
+            offsets = np.asarray(offsets, dtype=np.int64)
+            captured = np.asarray(captured, dtype=np.float64).reshape(offsets.shape[0], -1)
+            for a in range(0, offsets.shape[0], self.chunk):
+                o = offsets[a:a + self.chunk]
+                X = np.concatenate([x[o[:, q, None] + np.arange(s)] for q, s in enumerate(sizes)], axis=1)
+                r, J = run_np(tape, X, captured[a:a + self.chunk], dtype=LD)
+                terms, c0 = [], 0
+                for s in sizes:
+                    terms.append(np.ascontiguousarray(J[:, :, c0:c0 + s]))
+                    c0 += s
+                _correct(r, terms, loss)
+                out = []
+                for q, s in enumerate(sizes):
+                    terms[q] *= self.free[o[:, q, None] + np.arange(s)][:, None, :]
+                    out.append((terms[q], o[:, q]))
+                yield r, out
+
+
 def _scatter(out, first, contrib):
     """out[first[b] + j, :] += contrib[b, j, :] (long double: sort once, np.add.reduceat; np.bincount has no long double)."""
     order = np.argsort(first, kind="stable")

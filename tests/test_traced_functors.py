@@ -212,6 +212,10 @@ def test_recorded_versions_of_the_reference_spec_functors_give_its_values():
         xm[k] -= h
         fd = (np.array(run_tape(Trig().tape(), list(xp), [])) - np.array(run_tape(Trig().tape(), list(xm), []))) / (2 * h)
         np.testing.assert_allclose(j[0][:, k], fd, rtol=2e-8, atol=1e-9)
+    # ... and, tighter, against the extended-precision reference with its running error bound (tests/tape_reference.py)
+    import tape_reference as tr
+    ref = tr.reference(Trig().tape(), x)
+    assert tr.worst_ratio(ref, r, j[0]) <= 2.0
 
 
 @gpu
