@@ -17,7 +17,7 @@ constexpr int kWs = 32;
 constexpr int kWu = 28;  // ... of which the pair kernels read the first 28 (27 used)
 struct BalDev {
   int C, P, N;            // cameras (all, replicated), LOCAL points, LOCAL observations
-  int res_size, cam_size, pt_size;  // the problem's own block shape (r; c, q) <= (2; 9, 3) (bal_solver.hip: bal_block_shape); smaller shapes are padded
+  int res_size, cam_size, pt_size;  // the problem's own block shape (r; c, q) <= (2; 9, 3) (bal_plan.cpp: bal_block_shape); smaller shapes are padded
   // structure (built once on the host, point-major observation order)
   const int* cam;         // [N] camera of observation o
   const int* pt;          // [N] local point of observation o
@@ -35,7 +35,7 @@ struct BalDev {
   const int* long_segments;   // [num_long_segments]
   const int* pair_row_obs;  // [num_pairs] observation of camera i
   const int* pair_col_obs;  // [num_pairs] observation of camera j
-  // Retained points (bal_solver.hip, choose_retained_points): local points that are NOT eliminated — their three coordinates are rows
+  // Retained points (bal_plan.cpp, choose_retained_points): local points that are NOT eliminated — their three coordinates are rows
   // of the reduced system, three points to a PSEUDO-camera (a camera index of the layout with no observations and no parameters:
   // pseudo[i] != 0).  kept_pt[k]: the local point; kept_cam[k] = 3 * pseudo-camera + slot.  num_kept == 0 / pseudo == nullptr: none.
   int num_kept;
@@ -115,7 +115,7 @@ void launch_tri_pack(double* S, int ld, double* packed, int nblk, const int* col
 void launch_bal_eval_jac(const BalDev& d, hipStream_t s);
 void launch_bal_eval_cost(const BalDev& d, hipStream_t s);
 // the same two for a recorded functor (tape.hpp); bal_tape_width == 0: its register file does not fit the LDS
-int bal_tape_width(const Tape& t);
+// (int bal_tape_width(const Tape&): declared in problem.hpp, for the host planning)
 void launch_bal_eval_jac_tape(const BalDev& d, const TapeDevBuffers& tb, hipStream_t s);
 void launch_bal_eval_cost_tape(const BalDev& d, const TapeDevBuffers& tb, hipStream_t s);
 // the uploaded rows of the host-evaluated observations -> r / F / E planes (loss correction and column scaling as the

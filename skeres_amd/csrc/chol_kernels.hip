@@ -2006,10 +2006,8 @@ CholeskyPlan cholesky_plan(int nblk, int group, const int* last, bool chain, int
   plan.resident.assign(nblk, 0);
   plan.paired.assign(nblk, 0);
   if (group < 1) group = 1;
-  if (ncols < 0 || ncols > nblk) ncols = nblk;
-  if (tail_rows < 1 || ncols > nblk - tail_rows) tail_rows = 1;
-  const int tail_uniform = nblk - tail_rows;  // first block row of the tail
-  auto tail0_of = [&](int c) { return tail ? tail[c < nblk ? c : nblk - 1] : tail_uniform; };  // ... as block column c sees it (a profile: cholesky_factor)
+  const BlockEnvelope env(nblk, last, tail, ncols, tail_rows);
+  ncols = env.ncols; tail_rows = env.tail_rows;
   const bool partial = ncols < nblk;
   if (!chain || nblk < 3) {
     plan.bounds = cholesky_group_bounds(nblk, group);
@@ -2022,12 +2020,7 @@ CholeskyPlan cholesky_plan(int nblk, int group, const int* last, bool chain, int
     }
     return plan;
   }
-  auto last_main = [&](int c) { return last ? (last[c] < nblk - 1 ? last[c] : nblk - 1) : nblk - 1; };
-  auto count = [&](int first_row, int col) {  // active block rows of block column col from first_row: its run, and the tail rows
-    const int last_row = last_main(col);
-    const int main_rows = last_row >= first_row ? last_row - first_row + 1 : 0;
-    return main_rows + std::max(0, nblk - std::max(tail0_of(col), first_row + main_rows));
-  };
+  auto count = [&](int first_row, int col) { return env.active_rows(col, first_row); };
   const int jend = partial ? ncols : nblk - 1;  // block columns that have a column launch of their own
   for (int j = 0; j < jend; ++j)
     plan.resident[j] = count(j + 2, j) <= g_chain_max_trailing && 4 * count(j + 1, j) <= g_thin_grid;
@@ -3070,120 +3063,21 @@ void launch_syrk_gram(double* H, long ldh, const double* A, long lda, int Kc, in
 // lower-triangular 128x128 tiles incl. the diagonal tiles, 2*128*128*K each).
 double cholesky_syrk_flops(int npad, int group, const int* last, bool chain, double* c_tiles, int ncols, int tail_rows, const int* tail) {
   const int nblk = npad / 128;
-  if (ncols < 0 || ncols > nblk) ncols = nblk;
-  if (tail_rows < 1 || ncols > nblk - tail_rows) tail_rows = 1;
-  const CholeskyPlan plan = cholesky_plan(nblk, group, last, chain, ncols, tail_rows, tail);
+  const BlockEnvelope env(nblk, last, tail, ncols, tail_rows);
+  ncols = env.ncols;
+  const CholeskyPlan plan = cholesky_plan(nblk, group, last, chain, ncols, env.tail_rows, tail);
   const std::vector<int>& gb = plan.bounds;
   double f = 0.0, tiles = 0.0;
   for (size_t g = 0; g + 2 < gb.size(); ++g) {
     if (gb[g] >= ncols) break;
     const int k0 = gb[g], k1 = gb[g + 1];
     const int na = (plan.paired[k0] == 1 && k1 - k0 == 2) ? 0 : (plan.resident[k0] ? 1 : gb[g + 2] - k1);  // as cholesky_factor splits next(g) / syrk(g)
-    const int Lg = last ? (last[k1 - 1] < nblk - 1 ? last[k1 - 1] : nblk - 1) : nblk - 1;
-    const int first_row = k1 + na;
-    const int main_rows = Lg >= first_row ? Lg - first_row + 1 : 0;
-    const int tail0 = tail ? tail[k1 - 1] : nblk - tail_rows;  // (of the group's last column, as cholesky_factor takes them)
-    const int Tb = main_rows + std::max(0, nblk - std::max(tail0, first_row + main_rows));
+    const int Tb = env.active_rows(k1 - 1, k1 + na);  // (the rows of the group's last column, as cholesky_factor takes them)
     f += 0.5 * Tb * (Tb + 1.0) * 2.0 * 128.0 * 128.0 * (double)((k1 - k0) * 128);
     tiles += 0.5 * Tb * (Tb + 1.0);
   }
   if (c_tiles) *c_tiles = tiles;  // 128 x 128 tiles of C read and written once per launch, summed over the launches
   return f;
-}
-
-// Algorithmic flops of factoring the blocks inside the envelope (last == nullptr: every block): per block column with
-// h active block rows below it, 128^3 (1/3 + h + h^2) — diagonal factorisation, triangular solve of h blocks, symmetric
-// update of h (h + 1) / 2 blocks with its diagonal blocks counted once.  Sums to n^3 / 3 for a full matrix.
-double cholesky_plan_flops(int nblk, const int* last, int ncols, int tail_rows, const int* tail) {
-  double f = 0.0;
-  if (ncols < 0 || ncols > nblk) ncols = nblk;
-  if (tail_rows < 1 || ncols > nblk - tail_rows) tail_rows = 1;
-  for (int c = 0; c < ncols; ++c) {
-    const int tail0 = tail ? tail[c] : nblk - tail_rows;
-    const int lm = last ? (last[c] < nblk - 1 ? last[c] : nblk - 1) : nblk - 1;
-    const int main_rows = lm >= c + 1 ? lm - c : 0;
-    const double h = main_rows + std::max(0, nblk - std::max(tail0, c + 1 + main_rows));
-    f += 128.0 * 128.0 * 128.0 * (1.0 / 3.0 + h + h * h);
-  }
-  return f;
-}
-
-std::vector<int> root_envelope(const std::vector<int>& sep_off, int members_n, std::vector<int>* tail_out) {
-  const int nsep = (int)sep_off.size() - 1;
-  if (nsep <= 1) return {};
-  const int total = sep_off[nsep] + (members_n > 0 ? members_n : 0), nblk = (total + 1 + 127) / 128;
-  std::vector<int> first_col(nblk);
-  for (int i = 0; i < nblk; ++i) first_col[i] = i;
-  for (int k = 0; k < nsep; ++k) {
-    const int col = sep_off[k > 0 ? k - 1 : 0] / 128;
-    for (int r = sep_off[k] / 128; r <= (sep_off[k + 1] - 1) / 128 && r < nblk; ++r) first_col[r] = std::min(first_col[r], col);
-  }
-  if (members_n > 0 && tail_out) {
-    const int border_begin = sep_off[nsep] / 128;
-    for (int r = border_begin; r < nblk; ++r) first_col[r] = 0;
-    std::vector<int> last;
-    cholesky_envelope_bordered(first_col, border_begin, &last, tail_out);
-    return last;
-  }
-  return cholesky_envelope_last(first_col);
-}
-
-// Envelope from the block rows' first non-zero block columns (first_col[i] <= i for i < nblk-1; the entry of the
-// last block row is ignored: that row is always active): last[c] = max{ i <= nblk-2 : first_col[i] <= c }.
-std::vector<int> cholesky_envelope_last(const std::vector<int>& first_col, int tail_rows) {
-  const int nblk = (int)first_col.size();
-  if (tail_rows < 1) tail_rows = 1;
-  std::vector<int> last(nblk);
-  for (int c = 0; c < nblk; ++c) last[c] = c < nblk - 1 ? c : nblk - 1;
-  for (int i = 0; i + tail_rows < nblk; ++i) { const int c = first_col[i] < i ? first_col[i] : i; if (c >= 0 && last[c] < i) last[c] = i; }  // (the tail rows are active in every column anyway)
-  for (int c = 1; c < nblk; ++c) if (last[c] < last[c - 1]) last[c] = last[c - 1];
-  if (nblk >= 2 && last[nblk - 2] > nblk - 2) last[nblk - 2] = nblk - 2;
-  return last;
-}
-
-
-void cholesky_envelope_bordered(const std::vector<int>& first_col, int border_begin, std::vector<int>* last_out, std::vector<int>* tail_out) {
-  const int nblk = (int)first_col.size();
-  const int bb = std::max(0, std::min(border_begin, nblk - 1));
-  std::vector<int>& last = *last_out;
-  std::vector<int>& tail = *tail_out;
-  last.assign(nblk, 0); tail.assign(nblk, nblk - 1);
-  // the band: rows before the border
-  for (int c = 0; c < nblk; ++c) last[c] = c < bb ? c : nblk - 1;
-  for (int i = 0; i < bb; ++i) { const int c = first_col[i] < i ? first_col[i] : i; if (c >= 0 && last[c] < i) last[c] = i; }
-  for (int c = 1; c < bb; ++c) if (last[c] < last[c - 1]) last[c] = last[c - 1];
-  // the border: row i is active from reach[i] on — its own first column, or that of any border row before it (a column's tail rows
-  // are the LAST rows of the matrix: once row i is in, so is everything behind it); the right-hand-side row from column 0
-  std::vector<int> reach(nblk, 0);
-  int r = nblk;
-  for (int i = bb; i < nblk - 1; ++i) { r = std::min(r, std::max(0, std::min(first_col[i], i))); reach[i] = r; }
-  reach[nblk - 1] = 0;
-  for (int c = 0; c < nblk; ++c) {  // first active border row of column c: reach is non-increasing in i, so the rows active in column c are a suffix
-    int t = nblk - 1;
-    while (t - 1 >= bb && reach[t - 1] <= c) --t;
-    tail[c] = t;
-  }
-}
-
-std::vector<int> cholesky_row_first_cols(int nblk, const int* last, const int* tail, int tail_rows) {
-  std::vector<int> first(nblk, 0);
-  if (!last) return first;
-  int c0 = 0;
-  for (int kb = 0; kb < nblk; ++kb) {  // last is non-decreasing: one sweep
-    while (c0 < kb && last[c0] < kb) ++c0;
-    first[kb] = c0;
-  }
-  if (tail) {
-    for (int kb = 0; kb < nblk; ++kb) {  // ... or earlier, as a tail row (tail is non-increasing)
-      int c = 0;
-      while (c < first[kb] && tail[c] > kb) ++c;
-      first[kb] = c;
-    }
-  } else {
-    if (tail_rows < 1) tail_rows = 1;
-    for (int kb = std::max(0, nblk - tail_rows); kb < nblk; ++kb) first[kb] = 0;
-  }
-  return first;
 }
 
 }  // namespace sk

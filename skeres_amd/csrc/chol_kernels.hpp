@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "chol_envelope.hpp"
 #include "dev_knobs.hpp"
 
 namespace sk {
@@ -200,13 +201,6 @@ bool cholesky_chain_enabled(const CholeskyContext* ctx);
 bool cholesky_claim_pair_servers(CholeskyContext* ctx);
 void cholesky_release_pair_servers(CholeskyContext* ctx);
 void cholesky_disable_chain(CholeskyContext* ctx);
-struct CholeskyPlan {
-  std::vector<int> bounds;  // group start columns + nblk
-  std::vector<char> resident;  // per block column: under the resident panel chain
-  std::vector<char> paired;    // ... as the first (1) / second (2) column of a resident pair (one K = 256 SYRK for both); else 0
-};
-CholeskyPlan cholesky_plan(int nblk, int group, const int* last, bool chain, int ncols = -1, int tail_rows = 1, const int* tail = nullptr);
-int cholesky_plan_max_group(const CholeskyPlan& plan);
 // info != nullptr: one resident launch (bs_resident_kernel; a time-out of its polls raises *info to 2); nullptr: one launch per block step
 // zero_after (the resident launch only): every block below the diagonal that is read is overwritten with zeros once it is in
 // registers — the envelope is ready for the next assembly but for its diagonal blocks (BalSolver's reduced zero_envelope pass).
@@ -252,60 +246,6 @@ void cholesky_backsolve_front(double* S, long ld, int nblk, int ncols, int rhs_r
                               const int* yb_map = nullptr,  // yb_map (resident launch only): border index -> index into yb (< 0: zero) instead of a gathered copy
                               int resident = -1, bool prefilled = false);
 void cholesky_gather_map(const double* src, const int* map, double* dst, int m, hipStream_t s);
-// --- multi-way dissection: R segments of a block-banded system with R - 1 separators between them ---
-// Leaf front of one segment, in scalar rows.  The interior is followed by a border:
-//   first segment    [right separator, forward | rhs]                         tail_rows 1 — the head of the two-way case
-//   last segment     [left separator, REVERSED | rhs], interior reversed too  tail_rows 1 — the tail of the two-way case
-//   between two      [right separator, forward, padded to whole blocks | left separator, forward | rhs]
-//                    eliminated front to back: its last columns reach the right separator as part of their contiguous run;
-//                    the left separator couples with the FIRST columns and fills in along the whole interior (the spike):
-//                    its block rows are the tail rows of the partial factorisation (cholesky_plan).
-struct SegmentLayout {
-  int ncols = 0, nblk = 0, tail_rows = 1;
-  int rhs_row = 0;                    // absolute row of the right-hand side in the front
-  int right_off = -1, left_off = -1;  // first border row (relative to the border) of the right / left separator; -1: none
-  bool reversed = false;
-  bool spike = false;                 // a segment between two separators: the left one's rows reach every interior column
-};
-inline SegmentLayout segment_layout(int interior_n, int left_n, int right_n) {
-  SegmentLayout L;
-  L.ncols = (interior_n + 127) / 128;
-  if (left_n <= 0) {          // first segment (or the only one)
-    L.right_off = 0;
-    L.nblk = L.ncols + (right_n + 1 + 127) / 128;
-    L.rhs_row = L.ncols * 128 + right_n;
-  } else if (right_n <= 0) {  // last segment
-    L.left_off = 0; L.reversed = true;
-    L.nblk = L.ncols + (left_n + 1 + 127) / 128;
-    L.rhs_row = L.ncols * 128 + left_n;
-  } else {
-    const int rb = (right_n + 127) / 128;
-    L.right_off = 0; L.left_off = rb * 128; L.spike = true;
-    L.tail_rows = (left_n + 1 + 127) / 128;
-    L.nblk = L.ncols + rb + L.tail_rows;
-    L.rhs_row = L.ncols * 128 + L.left_off + left_n;
-  }
-  return L;
-}
-// Block envelope of the root (every separator in sequence order, then the right-hand side): separator k couples with
-// separator k - 1 through the Schur complement of the segment between them.  sep_off: R entries, scalar offset of each
-// separator in the root and, last, their total.  Empty result: dense (one separator).
-// members_n > 0: that many scalar rows behind the last separator couple with EVERY separator (the members of a border: pseudo-cameras of
-// retained points) — a border of the root in the sense of cholesky_envelope_bordered, its profile in *tail_out.
-std::vector<int> root_envelope(const std::vector<int>& sep_off, int members_n = 0, std::vector<int>* tail_out = nullptr);
-
-double cholesky_syrk_flops(int npad, int group, const int* last = nullptr, bool chain = false, double* c_tiles = nullptr, int ncols = -1, int tail_rows = 1,
-                           const int* tail = nullptr);
-double cholesky_plan_flops(int nblk, const int* last, int ncols = -1, int tail_rows = 1, const int* tail = nullptr);
-std::vector<int> cholesky_envelope_last(const std::vector<int>& first_col, int tail_rows = 1);
-// Bordered envelope of a whole system: block rows [border_begin, nblk) are the border (the last one carries the right-hand side).
-// From the block rows' first non-zero block columns: last[c] over the rows before the border (nblk - 1 for the border's own
-// columns), and the profile tail[c] = first border row active in column c — a border row, once reached, stays active, and so
-// does every border row behind it (the caller orders the border so that the rows reached first come last).
-void cholesky_envelope_bordered(const std::vector<int>& first_col, int border_begin, std::vector<int>* last, std::vector<int>* tail);
-// first block column in which block row i is active, for every i (from the envelope: the run `last`, the tail profile or uniform tail)
-std::vector<int> cholesky_row_first_cols(int nblk, const int* last, const int* tail, int tail_rows = 1);
-std::vector<int> cholesky_group_bounds(int nblk, int group);
 void launch_syrk_gram(double* H, long ldh, const double* A, long lda, int Kc, int nslabs, double* slabs, int tiles, hipStream_t s,
                       KernelTimer* kt);
 

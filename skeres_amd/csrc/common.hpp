@@ -16,6 +16,7 @@
 #include "functors.hpp"
 #include "loss.hpp"
 #include "parameterization.hpp"
+#include "problem.hpp"
 #include "tape.hpp"
 
 namespace sk {
@@ -60,77 +61,6 @@ struct DevBuf {
     return hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, s);
   }
   hipError_t zero(hipStream_t s) { return n ? hipMemsetAsync(p, 0, n * sizeof(T), s) : hipSuccess; }
-};
-
-// ---- host mirror of the reference objects ----------------------------------
-struct CostFunction {  // com.google.ceres.CostFunction as sized by CORE/SizedCostFunction.scala
-  int functor_id = 0;
-  std::vector<double> consts;
-  sk_evaluate_fn callback = nullptr;
-  void* user = nullptr;
-  int num_residuals = 0;
-  std::vector<int> block_sizes;
-  std::shared_ptr<const Tape> tape;  // SK_FUNCTOR_TAPE: the recorded body (consts: the captured doubles of THIS cost function)
-};
-
-// PredefinedLossFunctions (ceres.i:159-184): a flattened expression, children before parents; empty == trivial
-struct LossFunction {
-  std::vector<LossNode> nodes;
-  int root() const { return nodes.empty() ? -1 : (int)nodes.size() - 1; }
-};
-
-// PredefinedLocalParameterizations (ceres.i:186-210)
-struct LocalParameterization {
-  int type = kParamIdentity, global_size = 0, local_size = 0;
-  unsigned constant_mask = 0;  // subset: bit i = coordinate i held constant
-};
-
-struct Problem {  // CeresProblem; parameter blocks identified by pointer value
-  std::unordered_map<double*, int> block_of;
-  std::vector<double*> block_ptr;
-  std::vector<int> block_size;
-  // residual blocks (compact form)
-  std::vector<int> rb_functor;
-  std::vector<int> rb_num_residuals;
-  std::vector<size_t> rb_const_off;
-  std::vector<size_t> rb_pidx_off;  // size = blocks + 1
-  std::vector<int> rb_pidx;
-  std::vector<double> consts;
-  std::vector<const CostFunction*> rb_cost;  // non-null only for host-callback blocks
-  // recorded functor bodies, every distinct one once (by content: the caller may free its cost function); a tape block's
-  // rb_functor is kTapeFunctorBase + its index here
-  std::vector<std::shared_ptr<const Tape>> tapes;
-  std::unordered_map<std::string, int> tape_of;
-  int intern_tape(const std::shared_ptr<const Tape>& t) {
-    const std::string k = t->key();
-    auto it = tape_of.find(k);
-    if (it != tape_of.end()) return it->second;
-    tapes.push_back(t);
-    tape_of.emplace(k, (int)tapes.size() - 1);
-    return (int)tapes.size() - 1;
-  }
-  const Tape* tape_of_block(size_t b) const { const int f = rb_functor[b]; return f >= kTapeFunctorBase ? tapes[f - kTapeFunctorBase].get() : nullptr; }
-  // loss functions: every distinct loss expression once in loss_nodes (copied: the caller may free its object);
-  // rb_loss[b] = root node of block b's loss, -1 = trivial
-  std::vector<LossNode> loss_nodes;
-  std::vector<int> rb_loss;
-  std::unordered_map<std::string, int> loss_root_of;
-  bool has_loss = false;
-  int intern_loss(const LossFunction* l);
-  // local parameterizations: block_param[b] = index into params (copied: the caller may free its object), -1 = none;
-  // block_constant[b]: Problem::SetParameterBlockConstant
-  std::vector<LocalParameterization> params;
-  std::vector<int> block_param;
-  std::vector<char> block_constant;
-  bool has_parameterization() const {
-    for (size_t b = 0; b < block_ptr.size(); ++b)
-      if ((b < block_param.size() && block_param[b] >= 0) || (b < block_constant.size() && block_constant[b])) return true;
-    return false;
-  }
-  long num_residuals = 0;
-  bool has_callbacks = false;
-  Problem() { rb_pidx_off.push_back(0); }
-  int num_parameters() const { long s = 0; for (int b : block_size) s += b; return (int)s; }
 };
 
 struct Options {  // Solver.Options; Ceres 1.x defaults

@@ -11,20 +11,9 @@
 // Ceres build — see DESIGN.md §2.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "problem.hpp"  // LossType, LossNode
 
 namespace sk {
-
-enum LossType : int {
-  kLossTrivial = 0, kLossHuber = 1, kLossSoftLOne = 2, kLossCauchy = 3, kLossTukey = 4, kLossTolerant = 5, kLossComposed = 6, kLossScaled = 7
-};
-
-// One node of a flattened loss expression: children come before their parent.
-struct LossNode {
-  int type;
-  int f, g;     // children (composed: rho = f(g(s)); scaled: f), -1 = none (scaled: the NULL loss, rho = a s)
-  int depth;    // nesting depth below this node (leaves: 0)
-  double a, b;
-};
 
 constexpr int kLossMaxDepth = 4;                 // composed / scaled nesting accepted by sk_loss_composed / sk_loss_scaled
 constexpr double kLossMinPositive = 2.2250738585072014e-308;  // std::numeric_limits<double>::min()

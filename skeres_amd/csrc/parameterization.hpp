@@ -8,10 +8,10 @@
 // A constant parameter block (Problem::SetParameterBlockConstant) is kParamConstant: local size 0.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "problem.hpp"  // ParameterizationType
 
 namespace sk {
 
-enum ParameterizationType : int { kParamIdentity = 0, kParamSubset = 1, kParamQuaternion = 2, kParamHomogeneousVector = 3, kParamConstant = 4 };
 constexpr int kParamMaxSize = 16;  // global size of a parameterized block (the Jacobian lives in registers / on the stack)
 
 // One parameter block's parameterization, flattened for the device: `constant_mask` bit i set = coordinate i is held

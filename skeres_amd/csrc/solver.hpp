@@ -7,6 +7,7 @@
 #include <chrono>
 #include <memory>
 
+#include "bal_plan.hpp"
 #include "chol_kernels.hpp"
 #include "common.hpp"
 
@@ -75,16 +76,7 @@ class SolverBase {
 // BAL-shaped problems (2 residuals, one 9-block + one 3-block per residual
 // block): Schur elimination of the 3-blocks + dense Cholesky of the reduced system.
 std::unique_ptr<SolverBase> make_bal_solver(const Options& o, Problem* p);
-bool problem_is_bal_shaped(const Problem& p, std::string* why_not);
-void bal_index_problem(const Problem& p, std::vector<int>* cam_block, std::vector<int>* pt_block, std::vector<int>* ocam,
-                       std::vector<int>* opt);
-void bal_partition_points(const std::vector<int>& opt, int num_points, int world, std::vector<int>* cut);
-int bal_segment_plan(const Problem& p, int max_segments, bool forced, std::vector<int>* block_camera_part, std::vector<int>* block_point_owner);
-bool bal_block_shape(const Problem& p, int* r, int* c, int* q);
-int bal_border_plan(const Problem& p, int mode, std::vector<int>* final_index_of_block, int* gap, double* model_us, double* plain_us, double* fill);
-// the retained points as BalSolver::setup chooses them (one process): flag per residual block; returns their number
-int bal_retained_plan(const Problem& p, int mode, int max_points, int border_mode, std::vector<int>* retained_of_block, double* model_us, double* model_us_without,
-                      bool with_memory_order = true);
+// (the host planning of that path, and the plans as tests and tools read them: bal_plan.hpp)
 // Generic dense Jacobian path: DENSE_QR / DENSE_NORMAL_CHOLESKY.
 std::unique_ptr<SolverBase> make_dense_solver(const Options& o, Problem* p);
 // Tall dense rows over one parameter block (transposed Jacobian + long-K MFMA SYRK): DENSE_NORMAL_CHOLESKY.

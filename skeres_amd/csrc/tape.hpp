@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include "jet.hpp"
+#include "problem.hpp"  // TapeIns, Tape, kTapeFunctorBase
 
 namespace sk {
 
@@ -27,18 +28,6 @@ enum : int { kTapeReg = 0, kTapeParam = 1, kTapeObs = 2, kTapeConst = 3 };
 enum : int {
   kTapeMov = 0, kTapeAdd, kTapeSub, kTapeMul, kTapeDiv, kTapeNeg, kTapeSqrt, kTapeExp, kTapeLog, kTapeSin, kTapeCos, kTapeTan,
   kTapeAsin, kTapeAcos, kTapeAtan, kTapeAtan2, kTapeAbs, kTapeLt, kTapeLe, kTapeSelect, kTapeNumOps
-};
-struct TapeIns { int32_t op, dst, a, b, c; };  // dst: register; a, b, c: operands (SELECT: a = condition, b = then, c = else)
-
-// host copy (owned by the cost function, interned per problem by content)
-struct Tape {
-  int num_residuals = 0, num_registers = 0, num_obs_consts = 0;
-  std::vector<int> block_sizes;
-  std::vector<TapeIns> ins;
-  std::vector<double> consts;
-  std::vector<int32_t> out;  // operand per residual
-  int dim() const { int d = 0; for (int b : block_sizes) d += b; return d; }
-  std::string key() const;   // content key
 };
 // "" when well-formed, else what is wrong
 std::string tape_validate(const Tape& t);
@@ -143,7 +132,6 @@ __device__ __forceinline__ void tape_run(const TapeDev& t, const double* obs, co
 }
 #endif  // __HIPCC__
 
-constexpr int kTapeFunctorBase = 1000;  // Problem::rb_functor of a tape block = kTapeFunctorBase + index into Problem::tapes
 constexpr int kTapeMaxResiduals = 16, kTapeMaxDim = 64;
 constexpr size_t kTapeLdsBudget = 144 * 1024;
 // LDS bytes of the register file of `threads` threads at W derivative slots (W = 0: cost only)
