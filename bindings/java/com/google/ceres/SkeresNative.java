@@ -89,6 +89,10 @@ public final class SkeresNative {
   public static native void skOptionsFree(long o);
   public static native int skOptionsSetLinearSolverType(long o, int v);
   public static native int skOptionsSetMinimizerType(long o, int v);
+  public static native int skOptionsSetTrustRegionStrategyType(long o, int v);
+  public static native int skOptionsSetDoglegType(long o, int v);
+  public static native int skOptionsGetTrustRegionStrategyType(long o);
+  public static native int skOptionsGetDoglegType(long o);
   public static native int skOptionsSetMaxNumIterations(long o, int v);
   public static native int skOptionsSetMinimizerProgressToStdout(long o, int v);
   public static native int skOptionsSetFunctionTolerance(long o, double v);

@@ -291,6 +291,10 @@ SK_JNI(void, skOptionsFree)(JNIEnv* env, jclass c, jlong o) { (void)env; (void)c
 #define SK_OPT_DBL(jname, cname) SK_JNI(jint, jname)(JNIEnv* env, jclass c, jlong o, jdouble v) { (void)c; return check(env, cname(PTR(sk_options, o), v)); }
 SK_OPT_INT(skOptionsSetLinearSolverType, sk_options_set_linear_solver_type)
 SK_OPT_INT(skOptionsSetMinimizerType, sk_options_set_minimizer_type)
+SK_OPT_INT(skOptionsSetTrustRegionStrategyType, sk_options_set_trust_region_strategy_type)
+SK_OPT_INT(skOptionsSetDoglegType, sk_options_set_dogleg_type)
+SK_JNI(jint, skOptionsGetTrustRegionStrategyType)(JNIEnv* env, jclass c, jlong o) { (void)env; (void)c; return sk_options_get_trust_region_strategy_type(PTR(sk_options, o)); }
+SK_JNI(jint, skOptionsGetDoglegType)(JNIEnv* env, jclass c, jlong o) { (void)env; (void)c; return sk_options_get_dogleg_type(PTR(sk_options, o)); }
 SK_OPT_INT(skOptionsSetMaxNumIterations, sk_options_set_max_num_iterations)
 SK_OPT_INT(skOptionsSetMinimizerProgressToStdout, sk_options_set_minimizer_progress_to_stdout)
 SK_OPT_DBL(skOptionsSetFunctionTolerance, sk_options_set_function_tolerance)

@@ -59,6 +59,9 @@ class StdVectorInt {
 object Ownership extends Enumeration { val DO_NOT_TAKE_OWNERSHIP, TAKE_OWNERSHIP = Value }
 object LinearSolverType extends Enumeration { val DENSE_NORMAL_CHOLESKY = Value(0); val DENSE_QR = Value(1); val DENSE_SCHUR = Value(3) }
 object MinimizerType extends Enumeration { val LINE_SEARCH = Value(0); val TRUST_REGION = Value(1) }
+/** ceres::TrustRegionStrategyType / ceres::DoglegType (ceres/types.h through ceres.i:137). */
+object TrustRegionStrategyType extends Enumeration { val LEVENBERG_MARQUARDT = Value(0); val DOGLEG = Value(1) }
+object DoglegType extends Enumeration { val TRADITIONAL_DOGLEG = Value(0); val SUBSPACE_DOGLEG = Value(1) }
 /** ceres::NumericDiffMethodType (ceres/types.h through ceres.i:137).  A class with members, as SWIG's Java enums are: the reference
   * uses the name as a TYPE (CORE/NumericDiffCostFunction.scala:69, CORE/CostFunctor.scala:62) and imports its members
   * (`import NumericDiffMethodType._`, CORE/NumericDiffCostFunction.scala:80). */
@@ -157,6 +160,10 @@ object Solver {
     val handle: Long = SkeresNative.skOptionsNew()
     def setLinearSolverType(t: LinearSolverType.Value): Unit = SkeresNative.skOptionsSetLinearSolverType(handle, t.id)
     def setMinimizerType(t: MinimizerType.Value): Unit = SkeresNative.skOptionsSetMinimizerType(handle, t.id)
+    def setTrustRegionStrategyType(t: TrustRegionStrategyType.Value): Unit = SkeresNative.skOptionsSetTrustRegionStrategyType(handle, t.id)
+    def setDoglegType(t: DoglegType.Value): Unit = SkeresNative.skOptionsSetDoglegType(handle, t.id)
+    def trustRegionStrategyType: TrustRegionStrategyType.Value = TrustRegionStrategyType(SkeresNative.skOptionsGetTrustRegionStrategyType(handle))
+    def doglegType: DoglegType.Value = DoglegType(SkeresNative.skOptionsGetDoglegType(handle))
     def setMaxNumIterations(n: Int): Unit = SkeresNative.skOptionsSetMaxNumIterations(handle, n)
     def setMinimizerProgressToStdout(on: Boolean): Unit = SkeresNative.skOptionsSetMinimizerProgressToStdout(handle, if (on) 1 else 0)
     def setFunctionTolerance(v: Double): Unit = SkeresNative.skOptionsSetFunctionTolerance(handle, v)

@@ -55,6 +55,13 @@ typedef enum sk_linear_solver_type {
 /* ceres::MinimizerType; EX/Powell.scala:78 */
 typedef enum sk_minimizer_type { SK_LINE_SEARCH = 0, SK_TRUST_REGION = 1 } sk_minimizer_type;
 
+/* ceres::TrustRegionStrategyType and ceres::DoglegType (ceres/types.h, %include'd at ceres.i:137) */
+typedef enum sk_trust_region_strategy_type { SK_LEVENBERG_MARQUARDT = 0, SK_DOGLEG = 1 } sk_trust_region_strategy_type;
+typedef enum sk_dogleg_type {
+  SK_TRADITIONAL_DOGLEG = 0,
+  SK_SUBSPACE_DOGLEG = 1 /* not implemented: SK_ERR_UNSUPPORTED when the solver is created */
+} sk_dogleg_type;
+
 /* ceres::TerminationType, reported through Solver::Summary */
 typedef enum sk_termination_type {
   SK_CONVERGENCE = 0,
@@ -373,6 +380,23 @@ int sk_options_set_graph_replay(sk_options* o, int on);
 /* Several ranks, SK_DISTRIBUTION_SEGMENTED / AUTO: cut the camera sequence into at most n segments (0, the default: at
  * most one per rank; n >= 2 otherwise). */
 int sk_options_set_max_segments(sk_options* o, int n);
+/* Solver::Options::trust_region_strategy_type / dogleg_type (ceres/types.h via ceres.i:137; ceres/solver.h via ceres.i:151).
+ * LEVENBERG_MARQUARDT is the default.  DOGLEG (TRADITIONAL) follows Ceres 1.x's DoglegStrategy: the Gauss-Newton step and the
+ * Cauchy point depend on the Jacobian alone, so a rejected step is followed by a re-interpolation of the two vectors at half
+ * the radius — no assembly, no factorisation (sk_solver_stat "dogleg_reused_steps").  An out-of-range value returns
+ * SK_ERR_INVALID_ARGUMENT.  Refused with SK_ERR_UNSUPPORTED when the solver is created (sk_solver_create / sk_solve):
+ * SK_SUBSPACE_DOGLEG; DOGLEG in a world of more than one rank; DOGLEG on dense-row problems; and the two combinations that are
+ * not carried through: DOGLEG with tangent-space blocks (local parameterizations, constant blocks) on the dense Jacobian path
+ * (DENSE_QR / DENSE_NORMAL_CHOLESKY over residual blocks; DENSE_SCHUR takes constant blocks and subsets), and DOGLEG with
+ * host-evaluated (director) residual blocks under DENSE_SCHUR (the dense path takes them).  Under DOGLEG the iteration is
+ * enqueued launch by launch (sk_solver_stat "graph_replay" is 0). */
+int sk_options_set_trust_region_strategy_type(sk_options* o, int type);
+int sk_options_set_dogleg_type(sk_options* o, int type);
+/* The two fields read back, as a caller of the reference reads options.trust_region_strategy_type (a public field of
+ * Solver::Options, ceres/solver.h via ceres.i:151): what the setters left; the defaults are LEVENBERG_MARQUARDT and
+ * TRADITIONAL_DOGLEG. */
+int sk_options_get_trust_region_strategy_type(const sk_options* o);
+int sk_options_get_dogleg_type(const sk_options* o);
 enum { SK_BORDER_AUTO = 0, SK_BORDER_ON = 1, SK_BORDER_OFF = 2 };
 int sk_options_set_cholesky_border(sk_options* o, int mode);
 /* DENSE_SCHUR: RETAINED POINTS.  The Schur complement of a point seen by k cameras is a dense k x k square of camera blocks; a
@@ -517,6 +541,13 @@ int sk_solver_distribution(const sk_solver* s, double* allreduce_seconds, double
  * every solver:
  *   "phase_seconds_<i>"     seconds accumulated so far in phase i (0 Jacobians, 1 Schur assembly, 2 Cholesky, 3 back-substitution,
  *                           4 candidate cost, 5 all-reduce): sk_summary_phase_seconds, readable between steps
+ * DENSE_SCHUR and the dense Jacobian path, each counting since the solver was created:
+ *   "linear_solves"         factorisations (of the reduced system; of the normal equations, or QRs) enqueued
+ *   "dogleg_reused_steps"   DOGLEG: iterations whose step was re-interpolated from the vectors of an earlier one
+ *   "dogleg_mu"             DOGLEG: the current regularisation of the Gauss-Newton solve
+ *   "dogleg_w_r" "dogleg_m_r" "dogleg_w_w" "dogleg_w_m" "dogleg_m_m" "dogleg_g_g" "dogleg_g_p" "dogleg_p_p" "dogleg_a" "dogleg_b"
+ *                           DOGLEG: the scalars of the last linear solve (w = J s, m = J g over the observations; g-hat and
+ *                           the Gauss-Newton step p in the diagonal-scaled space) and the coefficients of the last step a s + b g
  * dense rows (DENSE_NORMAL_CHOLESKY over one parameter block):
  *   "jtj_flops_algorithmic" m n (n + 1): SURVEY.md section 8(d)'s figure for J^T J (sk_solver_syrk_flops_per_solve counts
  *                           the padded 128 x 128 tiles the launch computes) */

@@ -93,6 +93,10 @@ _SIGS = {
     "sk_options_free": (None, [C.c_void_p]),
     "sk_options_set_linear_solver_type": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_options_set_minimizer_type": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_options_set_trust_region_strategy_type": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_options_set_dogleg_type": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_options_get_trust_region_strategy_type": (C.c_int, [C.c_void_p]),
+    "sk_options_get_dogleg_type": (C.c_int, [C.c_void_p]),
     "sk_options_set_max_num_iterations": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_options_set_minimizer_progress_to_stdout": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_options_set_function_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
@@ -950,6 +954,14 @@ class MinimizerType:
     LINE_SEARCH, TRUST_REGION = 0, 1
 
 
+class TrustRegionStrategyType:  # ceres::TrustRegionStrategyType (ceres/types.h through ceres.i:137)
+    LEVENBERG_MARQUARDT, DOGLEG = 0, 1
+
+
+class DoglegType:  # ceres::DoglegType; SUBSPACE_DOGLEG is refused when the solver is created
+    TRADITIONAL_DOGLEG, SUBSPACE_DOGLEG = 0, 1
+
+
 class TerminationType:
     CONVERGENCE, NO_CONVERGENCE, FAILURE, USER_SUCCESS, USER_FAILURE = range(5)
 
@@ -1132,6 +1144,10 @@ class Solver:
 
         def setLinearSolverType(self, t): self._set("linear_solver_type", int(t))
         def setMinimizerType(self, t): self._set("minimizer_type", int(t))
+        def setTrustRegionStrategyType(self, t): self._set("trust_region_strategy_type", int(t))
+        def setDoglegType(self, t): self._set("dogleg_type", int(t))
+        def trustRegionStrategyType(self): return lib().sk_options_get_trust_region_strategy_type(self._h)
+        def doglegType(self): return lib().sk_options_get_dogleg_type(self._h)
         def setMaxNumIterations(self, n): self._set("max_num_iterations", int(n))
         def setMinimizerProgressToStdout(self, on): self._set("minimizer_progress_to_stdout", int(bool(on)))
         def setFunctionTolerance(self, v): self._set("function_tolerance", float(v))

@@ -14,6 +14,9 @@
 //   u   [3][N]   E^T F y_c (back-substitution)
 // Jacobi column scaling is folded into F / E as they are written.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+
 #include "functors.hpp"
 #include "bal_kernels.hpp"
 
@@ -1263,6 +1266,93 @@ void launch_bal_backsub(const BalDev& d, double* out, int norm_lo, int norm_hi, 
   rows.row[0] = 0; rows.count[0] = gc; rows.out[0] = out;
   rows.row[1] = 1; rows.count[1] = d.P > 0 ? gp + (d.num_kept > 0 ? 1 : 0) : 0; rows.out[1] = out + 1;
   launch_final_reduce_rows(d.partial, d.partial_stride, rows, s);
+}
+
+// ---------------------------------------------------------------------------
+// E. DOGLEG (common.hpp: namespace dogleg).  After a linear solve with D^2 = mu diag^2 the Gauss-Newton step g = -y sits in
+// step_c / step_p; the Cauchy direction is s = -(J_s^T r) / diag^2.  Every candidate of the iterations that share this Jacobian
+// is a s + b g: three kernels, and only the last runs again after a rejected step.
+// ---------------------------------------------------------------------------
+// Over the [cameras | points] vector: s and g to buffers of their own (accept_candidate swaps the parameter buffers, the next
+// linear solve overwrites step_*), and |g_hat|^2, g_hat . p, |p|^2 in the diag-scaled space (g_hat = gs / diag, p = diag g).
+// A pseudo-camera's slots of step_c hold the retained points' steps (bal_kept_step_kernel copied them to step_p): they are
+// counted there, as points, and not here.  A coordinate held constant has gs == 0 and a zero step: it adds zeros.
+__global__ __launch_bounds__(kBlock) void dogleg_vector_norms_kernel(BalDev d, DoglegDev q) {
+  double acc[3] = {0.0, 0.0, 0.0};
+  const int nc = 9 * d.C, n = nc + 3 * d.P;
+  for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
+    double sj = 0.0, gj = 0.0;
+    if (!(j < nc && d.pseudo && d.pseudo[j / 9])) {
+      const double diag = sqrt(fmin(fmax(d.colsq_c[j], d.lm_lo), d.lm_hi));
+      const double gh = d.gs_c[j] / diag;
+      gj = d.step_c[j];
+      const double p = diag * gj;
+      sj = -gh / diag;
+      acc[0] += gh * gh; acc[1] += gh * p; acc[2] += p * p;
+    }
+    q.s[j] = sj; q.g[j] = gj;
+  }
+  block_sum<3>(acc, q.partial + 5 * (size_t)q.stride, q.stride);
+}
+
+// Per observation w = F s_c + E s_p and m = F g_c + E g_p; the five sums w.r, m.r, |w|^2, w.m, |m|^2 (rows 0-4 of q.partial).
+// Lane o reads element o of each of the 26 planes once (every wave access one contiguous 512-byte run: 208 bytes per
+// observation) and gathers the two vectors through cam[o] / pt[o]; nothing per observation is written.
+__global__ __launch_bounds__(kBlock) void bal_dogleg_products_kernel(BalDev d, DoglegDev q) {
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  const size_t N = d.N;
+  const double* sp = q.s + 9 * (size_t)d.C;
+  const double* gp = q.g + 9 * (size_t)d.C;
+  for (int o = blockIdx.x * kBlock + threadIdx.x; o < d.N; o += gridDim.x * kBlock) {
+    const size_t ci = 9 * (size_t)d.cam[o], pi = 3 * (size_t)d.pt[o];
+    double w0 = 0.0, w1 = 0.0, m0 = 0.0, m1 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const double f0 = d.F[k * N + o], f1 = d.F[(9 + k) * N + o], sk_ = q.s[ci + k], gk = q.g[ci + k];
+      w0 += f0 * sk_; w1 += f1 * sk_; m0 += f0 * gk; m1 += f1 * gk;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double e0 = d.E[k * N + o], e1 = d.E[(3 + k) * N + o], sk_ = sp[pi + k], gk = gp[pi + k];
+      w0 += e0 * sk_; w1 += e1 * sk_; m0 += e0 * gk; m1 += e1 * gk;
+    }
+    const double r0 = d.r[o], r1 = d.r[N + o];
+    acc[0] += w0 * r0 + w1 * r1; acc[1] += m0 * r0 + m1 * r1;
+    acc[2] += w0 * w0 + w1 * w1; acc[3] += w0 * m0 + w1 * m1; acc[4] += m0 * m0 + m1 * m1;
+  }
+  block_sum<5>(acc, q.partial, q.stride);
+}
+
+// step = a s + b g; x_new = x + step * scale (a coordinate held constant: scale == 0, the candidate keeps its bits);
+// |x - x_new|^2 to row 8 of q.partial.  With the candidate cost this is all a re-interpolated iteration runs.
+__global__ __launch_bounds__(kBlock) void bal_dogleg_combine_kernel(BalDev d, DoglegDev q, double a, double b) {
+  double acc[1] = {0.0};
+  const int n = 9 * d.C + 3 * d.P;
+  for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
+    const double st = a * q.s[j] + b * q.g[j];
+    d.step_c[j] = st;
+    const double xo = d.xc[j];
+    const double xn = xo + st * d.scale_c[j];
+    d.xc_new[j] = xn;
+    const double df = xo - xn;
+    acc[0] += df * df;
+  }
+  block_sum<1>(acc, q.partial + 8 * (size_t)q.stride, q.stride);
+}
+
+int dogleg_partial_stride(const BalDev& d) { return std::max(grid_for(d.N), grid_for(9 * d.C + 3 * d.P)); }
+void launch_dogleg_vector_norms(const BalDev& d, const DoglegDev& q, hipStream_t s) {
+  hipLaunchKernelGGL(dogleg_vector_norms_kernel, dim3(grid_for(9 * d.C + 3 * d.P)), dim3(kBlock), 0, s, d, q);
+}
+void launch_bal_dogleg_products(const BalDev& d, const DoglegDev& q, hipStream_t s) {
+  hipLaunchKernelGGL(bal_dogleg_products_kernel, dim3(grid_for(d.N)), dim3(kBlock), 0, s, d, q);
+}
+// (rows 0-7 hold as many partial sums as their kernels have workgroups; the rest of each row was zeroed once and stays zero)
+void launch_dogleg_reduce_scalars(const DoglegDev& q, hipStream_t s) { launch_final_reduce(q.partial, q.stride, q.stride, 8, 0, q.scal, s); }
+void launch_bal_dogleg_combine(const BalDev& d, const DoglegDev& q, double a, double b, hipStream_t s) {
+  const int g = grid_for(9 * d.C + 3 * d.P);
+  hipLaunchKernelGGL(bal_dogleg_combine_kernel, dim3(g), dim3(kBlock), 0, s, d, q, a, b);
+  launch_final_reduce(q.partial + 8 * (size_t)q.stride, q.stride, g, 1, 0, q.scal + 8, s);
 }
 
 }  // namespace sk

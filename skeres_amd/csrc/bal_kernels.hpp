@@ -150,4 +150,15 @@ void launch_set_diagonal(double* S, int ld, int from, int to, double value, hipS
 // back-substitution and step (out[1] = |delta_p|^2)
 void launch_bal_backsub(const BalDev& d, double* out, int norm_lo, int norm_hi, int norm_lo2, int norm_hi2, hipStream_t s);
 
+// DOGLEG (bal_kernels.hip, section E).  s: the Cauchy direction -(J_s^T r) / diag^2, g: the Gauss-Newton step, both in the
+// solver's scaled space over [cameras | points]; partial: 9 rows of `stride` partial sums (zeroed once); scal[0..4]: w.r, m.r,
+// |w|^2, w.m, |m|^2 over the observations (w = J s, m = J g), scal[5..7]: |g_hat|^2, g_hat . p, |p|^2 in the diag-scaled
+// space, scal[8]: |x - x_new|^2 of the last combined step.
+struct DoglegDev { double* s; double* g; double* partial; int stride; double* scal; };
+int dogleg_partial_stride(const BalDev& d);
+void launch_dogleg_vector_norms(const BalDev& d, const DoglegDev& q, hipStream_t s);   // after launch_bal_backsub: reads step_*, colsq_*, gs_*, lm_lo / lm_hi
+void launch_bal_dogleg_products(const BalDev& d, const DoglegDev& q, hipStream_t s);   // 208 bytes per observation + two gathers
+void launch_dogleg_reduce_scalars(const DoglegDev& q, hipStream_t s);                  // rows 0-7 -> scal[0..7], fixed order
+void launch_bal_dogleg_combine(const BalDev& d, const DoglegDev& q, double a, double b, hipStream_t s);  // x_new = x + (a s + b g) scale; scal[8]
+
 }  // namespace sk

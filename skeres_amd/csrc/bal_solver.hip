@@ -127,7 +127,7 @@ class BalSolver : public SolverBase {
     if (name == "dissection_model_us_plain") { *value = cut_model_.t_plain; return true; }
     if (name == "dissection_model_us") { *value = cut_model_.t_model; return true; }
     if (name == "model_us_two_segments_with_members") { *value = cut_model_.two_segments_members_us; return true; }
-    return false;
+    return strategy_stat(name, value);
   }
   // the grouping is the library's choice (Options::cholesky_group == 0) and the masked streams of the resident panel chain exist
   // ... (the PLAN is then the one with resident runs; whether they really run resident or, with the same grouping, launch
@@ -146,6 +146,13 @@ class BalSolver : public SolverBase {
   int evaluate_with_jacobian(bool first) override;
   int try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) override;
   int try_step_once(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm, bool* chain_lost);
+  // DOGLEG: the linear solve is try_step_once with radius = 1 / mu, which then stops behind the back-substitution and leaves the
+  // eight scalars (DoglegDev::scal); the candidate of this radius — and of every smaller one after a rejection — is dogleg_candidate
+  int try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm);
+  int dogleg_candidate(double a, double b, double* new_cost, double* step_norm, bool* failed);
+  bool supports_dogleg() const override { return true; }
+  DoglegDev dl_{};
+  DevBuf<double> b_dl_vec_, b_dl_partial_, b_dl_scal_;
   void accept_candidate() override { std::swap(d_.xc, d_.xc_new); std::swap(d_.xp, d_.xp_new); parity_ ^= 1; }
   int write_back() override;
   void describe(Summary* s) override {
@@ -392,7 +399,12 @@ int BalSolver::init_queues() {
     // context exists, so that a reduced system of a few blocks pays neither the queue trial nor its 134 MB of scratch.
     bool host_or_tape = false;
     for (size_t b = 0; b < p.rb_functor.size() && !host_or_tape; ++b) host_or_tape = p.rb_functor[b] == SK_FUNCTOR_HOST_CALLBACK || p.tape_of_block(b) != nullptr;
-    graph_mode_ = npad_ / 128 <= 8 && !opt_.allreduce && !host_or_tape && opt_.dissection != SK_DISSECTION_ON && dev_knobs().dissect_at < 0 && opt_.graph_replay;
+    if (dogleg() && host_or_tape) {
+      for (size_t b = 0; b < p.rb_functor.size(); ++b)
+        if (p.rb_functor[b] == SK_FUNCTOR_HOST_CALLBACK) { set_error("DOGLEG with host-evaluated (director) residual blocks under DENSE_SCHUR is not supported"); return SK_ERR_UNSUPPORTED; }
+    }
+    // (DOGLEG: the captured sequences are Levenberg-Marquardt's — launch by launch)
+    graph_mode_ = npad_ / 128 <= 8 && !opt_.allreduce && !host_or_tape && opt_.dissection != SK_DISSECTION_ON && dev_knobs().dissect_at < 0 && opt_.graph_replay && !dogleg();
     if (graph_mode_) opt_.lookahead = false;  // one stream: the whole iteration is one in-order launch sequence
   }
   chol_ctx_.resident = chol_ctx_b_.resident = opt_.resident_kernels;
@@ -744,6 +756,15 @@ int BalSolver::allocate_fronts(const FrontLayout& lay) {
   SK_HIP_TRY(b_scal_.alloc(16)); SK_HIP_TRY(b_scal_.zero(s)); SK_HIP_TRY(b_small_.alloc(2 * 9 * (size_t)C_ + 6 * retained_pts_.size() + 64 + 16 * (size_t)opt_.world));
   fail_p_ = reinterpret_cast<int*>(b_scal_.p + 14); info_p_ = reinterpret_cast<int*>(b_scal_.p + 15);
   SK_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_scal_), 64 * sizeof(double), hipHostMallocDefault));
+  if (dogleg()) {
+    BalDev shape{}; shape.C = C_; shape.P = P_; shape.N = N_;
+    const size_t nx = 9 * (size_t)C_ + 3 * (size_t)P_;
+    dl_.stride = dogleg_partial_stride(shape);
+    SK_HIP_TRY(b_dl_vec_.alloc(2 * nx)); SK_HIP_TRY(b_dl_vec_.zero(s));
+    SK_HIP_TRY(b_dl_partial_.alloc(9 * (size_t)dl_.stride)); SK_HIP_TRY(b_dl_partial_.zero(s));
+    SK_HIP_TRY(b_dl_scal_.alloc(16)); SK_HIP_TRY(b_dl_scal_.zero(s));
+    dl_.s = b_dl_vec_.p; dl_.g = b_dl_vec_.p + nx; dl_.partial = b_dl_partial_.p; dl_.scal = b_dl_scal_.p;
+  }
   return SK_OK;
 }
 
@@ -1012,6 +1033,7 @@ int BalSolver::evaluate_with_jacobian(bool first) {
 // that factorisation, not the step: the chain is switched off for the device and the same linear system is assembled
 // and factored again, launch by launch, in the same iteration — the trajectory does not change.
 int BalSolver::try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
+  if (dogleg()) return try_step_dogleg(radius, valid, mcc, new_cost, step_norm);
   bool chain_lost = false;
   int rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
   if (rc == SK_OK && chain_lost) rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
@@ -1023,6 +1045,7 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
   *chain_lost = false;
   const size_t nc = 9 * (size_t)C_;
   *valid = false;
+  ++n_linear_solves_;
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   const bool graph = graph_ok();
   const bool replay = graph && g_step_[parity_] != nullptr;
@@ -1140,7 +1163,14 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
     }
     launch_bal_backsub(d_, b_scal_.p + 8, lo, hi, lo2, hi2, s);  // (|delta_c|^2 to slot 8, |delta_p|^2 to slot 9)
   }
+  if (dogleg()) {  // the two vectors of this Jacobian and their eight scalars (counted with the back-substitution)
+    kt_.begin("dogleg_vector_norms", s); launch_dogleg_vector_norms(d_, dl_, s); kt_.end("dogleg_vector_norms", s);
+    kt_.begin("bal_dogleg_products", s); launch_bal_dogleg_products(d_, dl_, s); kt_.end("bal_dogleg_products", s);
+    launch_dogleg_reduce_scalars(dl_, s);
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, dl_.scal, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
   if (!graph) SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
+  if (!dogleg()) {  // (DOGLEG: the candidate is formed and evaluated by dogleg_candidate)
   kt_.begin("bal_eval_cost", s);
   if (tape_mode_) launch_bal_eval_cost_tape(d_, tape_dev_, s); else launch_bal_eval_cost(d_, s);
   kt_.end("bal_eval_cost", s);
@@ -1151,6 +1181,7 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
     nb_cost += launch_bal_host_cost(d_, nb_cost, s);
   }
   launch_final_reduce(b_partial_.p, partial_stride_, nb_cost, 2, 0, b_scal_.p, s);
+  }
   if (!graph) SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
   SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 16 * sizeof(double), hipMemcpyDeviceToHost, s));  // scalars 0-9, the two flags in 14 and 15
   }
@@ -1184,6 +1215,7 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
     *chain_lost = true;
     return SK_OK;
   }
+  if (dogleg()) { *valid = (fail | info) == 0; return SK_OK; }  // (one device; the scalars are in h_scal_[16..23])
   // sum r_new^2, model term, |delta_p|^2 (segmented: + this rank's cameras' |delta_c|^2, which no other rank has), failure
   double loc[4] = {h_scal_[0], h_scal_[1], h_scal_[9] + (segmented_ ? h_scal_[8] : 0.0), (double)(fail | info)};
   const int ops4[4] = {0, 0, 0, 1};
@@ -1196,6 +1228,59 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
   *mcc = -loc[1];
   *new_cost = candidate_failed ? std::numeric_limits<double>::max() : 0.5 * loc[0];
   *step_norm = std::sqrt(step_sq);
+  return SK_OK;
+}
+
+// DOGLEG (common.hpp: namespace dogleg).  A new Jacobian: the Gauss-Newton solve at the current mu, again at ten times
+// mu while the factorisation finds the system not positive definite; then, and after every rejected step, the candidate of the
+// radius from the two vectors on the device.
+int BalSolver::try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
+  *valid = false;
+  d_.lm_lo = opt_.min_lm_diagonal; d_.lm_hi = opt_.max_lm_diagonal;
+  if (!dl_reuse_) {
+    bool solved = false;
+    while (dl_mu_ < dogleg::kMaxMu) {
+      bool chain_lost = false, ok = false;
+      int rc = try_step_once(1.0 / dl_mu_, &ok, mcc, new_cost, step_norm, &chain_lost);
+      if (rc == SK_OK && chain_lost) rc = try_step_once(1.0 / dl_mu_, &ok, mcc, new_cost, step_norm, &chain_lost);
+      if (rc) return rc;
+      if (ok && !chain_lost) { solved = true; break; }
+      // not ok: the factorisation met a pivot that is not positive, or a point block's 3 x 3 did (the fail flag); both mean the
+      // damped system is not positive definite at this mu, and each further solve counts in "linear_solves"
+      dl_mu_ *= dogleg::kMuIncreaseFactor;
+    }
+    if (!solved) return SK_OK;  // invalid step
+    dl_k_ = dogleg::Scalars::from(h_scal_ + 16);
+  } else {
+    ++n_dl_reused_;
+  }
+  if (!dogleg::interpolate(dl_k_, radius, &dl_a_, &dl_b_, &dl_step_norm_, mcc)) return SK_OK;
+  bool failed = false;
+  int rc = dogleg_candidate(dl_a_, dl_b_, new_cost, step_norm, &failed);
+  if (rc) return rc;
+  *valid = !failed;
+  return SK_OK;
+}
+
+int BalSolver::dogleg_candidate(double a, double b, double* new_cost, double* step_norm, bool* failed) {
+  hipStream_t s = stream_;
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
+  kt_.begin("bal_dogleg_combine", s); launch_bal_dogleg_combine(d_, dl_, a, b, s); kt_.end("bal_dogleg_combine", s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
+  kt_.begin("bal_eval_cost", s);
+  if (tape_mode_) launch_bal_eval_cost_tape(d_, tape_dev_, s); else launch_bal_eval_cost(d_, s);  // (its model term: not used here)
+  kt_.end("bal_eval_cost", s);
+  launch_final_reduce(b_partial_.p, partial_stride_, bal_partial_blocks(N_), 1, 0, b_scal_.p, s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 24, dl_.scal + 8, sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
+  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
+  *failed = !std::isfinite(h_scal_[24]);
+  *new_cost = 0.5 * h_scal_[0];
+  *step_norm = std::sqrt(h_scal_[24]);
   return SK_OK;
 }
 

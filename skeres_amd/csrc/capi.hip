@@ -560,6 +560,16 @@ int sk_options_set_minimizer_type(sk_options* o, int t) {
   if (t != SK_TRUST_REGION) { set_error("only TRUST_REGION is implemented"); return SK_ERR_UNSUPPORTED; }
   o->o.minimizer_type = t; return SK_OK;
 }
+int sk_options_set_trust_region_strategy_type(sk_options* o, int t) {
+  if (t != SK_LEVENBERG_MARQUARDT && t != SK_DOGLEG) { set_error("invalid trust region strategy type %d", t); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.trust_region_strategy_type = t; return SK_OK;
+}
+int sk_options_set_dogleg_type(sk_options* o, int t) {  // (SUBSPACE_DOGLEG is a valid value; a solver with DOGLEG refuses it when it is created)
+  if (t != SK_TRADITIONAL_DOGLEG && t != SK_SUBSPACE_DOGLEG) { set_error("invalid dogleg type %d", t); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.dogleg_type = t; return SK_OK;
+}
+int sk_options_get_trust_region_strategy_type(const sk_options* o) { return o->o.trust_region_strategy_type; }
+int sk_options_get_dogleg_type(const sk_options* o) { return o->o.dogleg_type; }
 int sk_options_set_max_num_iterations(sk_options* o, int n) { if (n < 0) { set_error("max_num_iterations must be >= 0"); return SK_ERR_INVALID_ARGUMENT; } o->o.max_num_iterations = n; return SK_OK; }
 int sk_options_set_minimizer_progress_to_stdout(sk_options* o, int on) { o->o.progress_to_stdout = on != 0; return SK_OK; }
 #define SK_SET_D(NAME, FIELD) int sk_options_set_##NAME(sk_options* o, double v) { if (!(v >= 0.0)) { set_error(#NAME " must be >= 0"); return SK_ERR_INVALID_ARGUMENT; } o->o.FIELD = v; return SK_OK; }

@@ -67,6 +67,7 @@ struct Options {  // Solver.Options; Ceres 1.x defaults
   int linear_solver_type = SK_DENSE_QR;  // ceres default is SPARSE_NORMAL_CHOLESKY when built with a sparse backend, else DENSE_QR
   int linear_solver_type_given = -1;     // set when the solver in use is an alternate for the one asked for (capi.hip: make_solver)
   int minimizer_type = SK_TRUST_REGION;
+  int trust_region_strategy_type = SK_LEVENBERG_MARQUARDT, dogleg_type = SK_TRADITIONAL_DOGLEG;
   int max_num_iterations = 50;
   bool progress_to_stdout = false;
   double function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
@@ -98,6 +99,22 @@ struct Options {  // Solver.Options; Ceres 1.x defaults
   int retained = SK_RETAINED_AUTO, retained_max = 0;  // DENSE_SCHUR: the points with the widest tracks stay in the reduced system (sk_options_set_retained_points)
 };
 
+// Traditional dogleg as published for Ceres 1.x's DoglegStrategy: recalled, not pinned (like SURVEY.md §8a row a13), so the
+// constants live here and nowhere else.
+namespace dogleg {
+constexpr double kMinMu = 1e-8, kMaxMu = 1.0, kMuIncreaseFactor = 10.0;
+constexpr double kIncreaseThreshold = 0.75, kDecreaseThreshold = 0.25;
+constexpr double kRadiusDecreaseFactor = 0.5, kRadiusGrowth = 3.0, kMuDecrease = 2.0;  // mu <- max(min_mu, 2 mu / 10) after an accepted step
+// the scalars of one linear solve: the observation products (w = J s, m = J g) and the vector norms in the diagonal-scaled space
+struct Scalars {
+  double w_r = 0, m_r = 0, w_w = 0, w_m = 0, m_m = 0, g_g = 0, g_p = 0, p_p = 0;
+  static Scalars from(const double* k) { return {k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7]}; }  // in the order the kernels leave them
+};
+// step = a s + b g for this radius (s = -g_hat / diag, the Cauchy direction; g, the Gauss-Newton step), its norm in the
+// diagonal-scaled space and the model's cost decrease.  false: no step can be formed from these scalars.
+bool interpolate(const Scalars& k, double radius, double* a, double* b, double* step_norm, double* model_cost_change);
+}  // namespace dogleg
+
 struct IterationLog {
   int iteration = 0;
   double cost = 0, cost_change = 0, gradient_max_norm = 0, step_norm = 0, relative_decrease = 0,
@@ -119,6 +136,7 @@ struct Summary {
   int linear_solver_type_given = -1;  // what Solver.Options asked for when the solver used is its alternate (Ceres: "Given / Used")
   int num_e_blocks = 0, num_f_blocks = 0;
   int world = 1;
+  int trust_region_strategy_type = SK_LEVENBERG_MARQUARDT;
   std::string device_name;
   std::string brief, full;
   void build_reports();

@@ -337,6 +337,62 @@ __global__ __launch_bounds__(256) void dense_model_kernel(const double* J, const
   for (int w = 128; w > 0; w >>= 1) { if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
   if (threadIdx.x == 0) out[0] = sh[0];
 }
+// DOGLEG (common.hpp: namespace dogleg), the dense path's three passes in the style of the kernels above.
+// After the linear solve with D^2 = mu diag^2: g = -y (Gauss-Newton step), s = -gs / diag^2 (Cauchy direction), both in the scaled
+// space; out[0..2] = |g_hat|^2, g_hat . p, |p|^2 in the diag-scaled space (g_hat = gs / diag, p = diag g).
+__global__ __launch_bounds__(256) void dense_dogleg_vectors_kernel(const double* colsq, const double* gs, const double* y, int n, double lo, double hi,
+                                                                    double* s_out, double* g_out, double* out) {
+  __shared__ double sh[3][256];
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const double diag = sqrt(fmin(fmax(colsq[j], lo), hi));
+    const double gh = gs[j] / diag, g = -y[j], p = diag * g;
+    s_out[j] = -gh / diag; g_out[j] = g;
+    a0 += gh * gh; a1 += gh * p; a2 += p * p;
+  }
+  sh[0][threadIdx.x] = a0; sh[1][threadIdx.x] = a1; sh[2][threadIdx.x] = a2;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) for (int k = 0; k < 3; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) out[threadIdx.x] = sh[threadIdx.x][0];
+}
+// out[0..4] = w.r, m.r, |w|^2, w.m, |m|^2 with w = J s, m = J g: both matrix-vector products in one pass over J
+__global__ __launch_bounds__(256) void dense_dogleg_products_kernel(const double* J, const double* r, const double* sv, const double* gv, int m, int n, double* out) {
+  __shared__ double sh[5][256];
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int i = threadIdx.x; i < m; i += 256) {
+    double w = 0.0, mm = 0.0;
+    for (int j = 0; j < n; ++j) { const double v = J[(size_t)i * n + j]; w += v * sv[j]; mm += v * gv[j]; }
+    acc[0] += w * r[i]; acc[1] += mm * r[i]; acc[2] += w * w; acc[3] += w * mm; acc[4] += mm * mm;
+  }
+  for (int k = 0; k < 5; ++k) sh[k][threadIdx.x] = acc[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) for (int k = 0; k < 5; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x < 5) out[threadIdx.x] = sh[threadIdx.x][0];
+}
+// step = a s + b g ; x_new = x + step * scale ; out[0] = |x - x_new|^2
+__global__ __launch_bounds__(256) void dense_dogleg_combine_kernel(const double* sv, const double* gv, double a, double b, const double* scale, const double* x,
+                                                                    double* step, double* x_new, int n, double* out) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const double st = a * sv[j] + b * gv[j];
+    step[j] = st;
+    const double xn = x[j] + st * scale[j];
+    x_new[j] = xn;
+    const double d = x[j] - xn;
+    s += d * d;
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) { if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
+  if (threadIdx.x == 0) out[0] = sh[0];
+}
 // out[0] = max_j |gs_j / scale_j| ; out[1] = |x|^2
 __global__ __launch_bounds__(256) void dense_gmax_kernel(const double* gs, const double* scale, const double* x, int n, double* out) {
   __shared__ double shm[256], shs[256];
@@ -476,6 +532,15 @@ void launch_dense_scale(double* J, const double* scale, int m, int n, hipStream_
 void launch_dense_sumsq(const double* r, int m, double* out, hipStream_t s) { hipLaunchKernelGGL(dense_sumsq_kernel, dim3(1), dim3(256), 0, s, r, m, out); }
 void launch_dense_normal(const double* J, const double* r, int m, int n, double* H, int ld, int rhs_row, hipStream_t s) { const int e = n * (n + 1); hipLaunchKernelGGL(dense_normal_kernel, dim3((e + 255) / 256), dim3(256), 0, s, J, r, m, n, H, ld, rhs_row); }
 void launch_dense_step(const double* y, const double* scale, const double* x, double* step, double* x_new, int n, double* out, hipStream_t s) { hipLaunchKernelGGL(dense_step_kernel, dim3(1), dim3(256), 0, s, y, scale, x, step, x_new, n, out); }
+void launch_dense_dogleg_vectors(const double* colsq, const double* gs, const double* y, int n, double lo, double hi, double* s_out, double* g_out, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(dense_dogleg_vectors_kernel, dim3(1), dim3(256), 0, s, colsq, gs, y, n, lo, hi, s_out, g_out, out);
+}
+void launch_dense_dogleg_products(const double* J, const double* r, const double* sv, const double* gv, int m, int n, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(dense_dogleg_products_kernel, dim3(1), dim3(256), 0, s, J, r, sv, gv, m, n, out);
+}
+void launch_dense_dogleg_combine(const double* sv, const double* gv, double a, double b, const double* scale, const double* x, double* step, double* x_new, int n, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(dense_dogleg_combine_kernel, dim3(1), dim3(256), 0, s, sv, gv, a, b, scale, x, step, x_new, n, out);
+}
 void launch_dense_model(const double* J, const double* r, const double* step, int m, int n, double* out, hipStream_t s) { hipLaunchKernelGGL(dense_model_kernel, dim3(1), dim3(256), 0, s, J, r, step, m, n, out); }
 void launch_dense_gmax(const double* gs, const double* scale, const double* x, int n, double* out, hipStream_t s) { hipLaunchKernelGGL(dense_gmax_kernel, dim3(1), dim3(256), 0, s, gs, scale, x, n, out); }
 void launch_dense_qr(const double* J, const double* r, const double* D, int m, int n, double* A, double* b, double* y, int* ok, hipStream_t s) {

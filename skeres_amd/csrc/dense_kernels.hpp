@@ -57,6 +57,11 @@ void launch_dense_sumsq(const double* r, int m, double* out, hipStream_t s);
 void launch_dense_normal(const double* J, const double* r, int m, int n, double* H, int ld, int rhs_row, hipStream_t s);
 void launch_dense_step(const double* y, const double* scale, const double* x, double* step, double* x_new, int n, double* out, hipStream_t s);
 void launch_dense_model(const double* J, const double* r, const double* step, int m, int n, double* out, hipStream_t s);
+// DOGLEG (common.hpp: namespace dogleg): g = -y and s = -gs / diag^2 with out[0..2] = |g_hat|^2, g_hat . p, |p|^2; out[0..4] = w.r, m.r,
+// |w|^2, w.m, |m|^2 (w = J s, m = J g); the candidate x_new = x + (a s + b g) scale with out[0] = |x - x_new|^2
+void launch_dense_dogleg_vectors(const double* colsq, const double* gs, const double* y, int n, double lo, double hi, double* s_out, double* g_out, double* out, hipStream_t s);
+void launch_dense_dogleg_products(const double* J, const double* r, const double* sv, const double* gv, int m, int n, double* out, hipStream_t s);
+void launch_dense_dogleg_combine(const double* sv, const double* gv, double a, double b, const double* scale, const double* x, double* step, double* x_new, int n, double* out, hipStream_t s);
 void launch_dense_gmax(const double* gs, const double* scale, const double* x, int n, double* out, hipStream_t s);
 void launch_dense_qr(const double* J, const double* r, const double* D, int m, int n, double* A, double* b, double* y, int* ok, hipStream_t s);
 

@@ -26,6 +26,11 @@ class DenseSolver : public SolverBase {
   int setup() override;
   int evaluate_with_jacobian(bool first) override;
   int try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) override;
+  // DOGLEG over residual blocks without tangent-space blocks (setup() refuses those): the linear solve at radius 1 / mu, then, and
+  // after every rejected step, the candidate of the radius from s and g
+  int try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm);
+  int enqueue_linear_solve(double radius);  // D from the radius, the normal equations or the QR, y; records kEvAssemble and kEvChol
+  bool supports_dogleg() const override { return true; }
   void accept_candidate() override { std::swap(x_, x_new_); }
   int write_back() override;
   void describe(Summary* s) override {
@@ -51,10 +56,11 @@ class DenseSolver : public SolverBase {
       *value = (double)c;
       return true;
     }
-    return false;
+    return strategy_stat(name, value);
   }
 
  private:
+  DevBuf<double> b_dl_vec_, b_dl_scal_;  // DOGLEG: [s | g]; the eight scalars and |x - x_new|^2
   int evaluate(const double* x_dev, bool jac);
   int host_callbacks(const double* x_dev, bool jac);
 
@@ -96,6 +102,7 @@ int DenseSolver::setup() {
   for (size_t b = 0; b < p.block_size.size(); ++b) { block_off_[b] = ng_; ng_ += p.block_size[b]; }
   n_ = ng_;
   tangent_ = p.has_parameterization();
+  if (dogleg() && tangent_) { set_error("DOGLEG with local parameterizations or constant blocks on the dense Jacobian path is not supported (DENSE_SCHUR takes constant blocks and subsets)"); return SK_ERR_UNSUPPORTED; }
   std::vector<ParamBlock> pblocks;
   if (tangent_) {
     n_ = 0;
@@ -172,6 +179,7 @@ int DenseSolver::setup() {
   SK_HIP_TRY(b_y_.alloc(npad_)); SK_HIP_TRY(b_w_.alloc(npad_)); SK_HIP_TRY(b_scal_.alloc(16));
   SK_HIP_TRY(b_fail_.alloc(1)); SK_HIP_TRY(b_fail_.zero(s)); SK_HIP_TRY(b_info_.alloc(1)); SK_HIP_TRY(b_info_.zero(s)); SK_HIP_TRY(b_ok_.alloc(1));
   SK_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_scal_), 64 * sizeof(double), hipHostMallocDefault));
+  if (dogleg()) { SK_HIP_TRY(b_dl_vec_.alloc(2 * (size_t)n_)); SK_HIP_TRY(b_dl_scal_.alloc(16)); SK_HIP_TRY(b_dl_scal_.zero(s)); }
   SK_HIP_TRY(hipStreamSynchronize(s));
   return SK_OK;
 }
@@ -269,10 +277,9 @@ int DenseSolver::evaluate_with_jacobian(bool first) {
   return SK_OK;
 }
 
-int DenseSolver::try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
+int DenseSolver::enqueue_linear_solve(double radius) {
   hipStream_t s = stream_;
-  *valid = false;
-  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
+  ++n_linear_solves_;
   launch_lm_diagonal(b_colsq_.p, b_D_.p, n_, opt_.min_lm_diagonal, opt_.max_lm_diagonal, radius, s);
   SK_HIP_TRY(hipMemsetAsync(b_info_.p, 0, sizeof(int), s));
   SK_HIP_TRY(hipMemsetAsync(b_fail_.p, 0, sizeof(int), s));
@@ -289,11 +296,21 @@ int DenseSolver::try_step(double radius, bool* valid, double* mcc, double* new_c
     launch_dense_qr(b_J_.p, b_r_.p, b_D_.p, m_, n_, b_A_.p, b_b_.p, b_y_.p, b_ok_.p, s);
   }
   SK_HIP_TRY(hipEventRecord(ev_[kEvChol], s));
+  return SK_OK;
+}
+
+int DenseSolver::try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
+  if (dogleg()) return try_step_dogleg(radius, valid, mcc, new_cost, step_norm);
+  hipStream_t s = stream_;
+  *valid = false;
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
+  int rc = enqueue_linear_solve(radius);
+  if (rc) return rc;
   if (tangent_) launch_dense_plus(b_y_.p, b_scale_.p, x_, b_step_.p, x_new_, b_pblocks_.p, num_pblocks_, b_scal_.p, s);
   else launch_dense_step(b_y_.p, b_scale_.p, x_, b_step_.p, x_new_, n_, b_scal_.p, s);
   launch_dense_model(b_J_.p, b_r_.p, b_step_.p, m_, n_, b_scal_.p + 1, s);
   SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
-  int rc = evaluate(x_new_, false);
+  rc = evaluate(x_new_, false);
   const bool eval_failed = rc == SK_ERR_EVALUATION_FAILED;
   if (rc && !eval_failed) return rc;
   if (has_loss_) { apply_loss(b_rc_.p, false); launch_dense_sum(b_cterm_.p, m_, b_scal_.p + 2, s); }
@@ -315,6 +332,64 @@ int DenseSolver::try_step(double radius, bool* valid, double* mcc, double* new_c
   *valid = true;
   *step_norm = std::sqrt(h_scal_[0]);
   *mcc = -h_scal_[1];
+  *new_cost = (fail || eval_failed) ? std::numeric_limits<double>::infinity() : 0.5 * h_scal_[2];
+  return SK_OK;
+}
+
+int DenseSolver::try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
+  hipStream_t s = stream_;
+  *valid = false;
+  float ms = 0.f;
+  double* sv = b_dl_vec_.p;
+  double* gv = b_dl_vec_.p + n_;
+  if (!dl_reuse_) {
+    bool solved = false;
+    while (dl_mu_ < dogleg::kMaxMu) {
+      SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
+      int rc = enqueue_linear_solve(1.0 / dl_mu_);
+      if (rc) return rc;
+      launch_dense_dogleg_vectors(b_colsq_.p, b_gs_.p, b_y_.p, n_, opt_.min_lm_diagonal, opt_.max_lm_diagonal, sv, gv, b_dl_scal_.p + 5, s);
+      launch_dense_dogleg_products(b_J_.p, b_r_.p, sv, gv, m_, n_, b_dl_scal_.p, s);
+      SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
+      SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 24, b_dl_scal_.p, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+      SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 17, b_info_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 18, b_ok_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      SK_HIP_TRY(hipStreamSynchronize(s));
+      if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvAssemble]) == hipSuccess) phase_[1] += 1e-3 * ms;
+      if (hipEventElapsedTime(&ms, ev_[kEvAssemble], ev_[kEvChol]) == hipSuccess) phase_[2] += 1e-3 * ms;
+      if (hipEventElapsedTime(&ms, ev_[kEvChol], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
+      int info = 0, ok = 1;
+      std::memcpy(&info, h_scal_ + 17, sizeof(int)); std::memcpy(&ok, h_scal_ + 18, sizeof(int));
+      if (!info && ok) { solved = true; break; }
+      dl_mu_ *= dogleg::kMuIncreaseFactor;
+    }
+    if (!solved) return SK_OK;  // invalid step
+    dl_k_ = dogleg::Scalars::from(h_scal_ + 24);
+  } else {
+    ++n_dl_reused_;
+  }
+  if (!dogleg::interpolate(dl_k_, radius, &dl_a_, &dl_b_, &dl_step_norm_, mcc)) return SK_OK;
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
+  SK_HIP_TRY(hipMemsetAsync(b_fail_.p, 0, sizeof(int), s));
+  launch_dense_dogleg_combine(sv, gv, dl_a_, dl_b_, b_scale_.p, x_, b_step_.p, x_new_, n_, b_dl_scal_.p + 8, s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
+  int rc = evaluate(x_new_, false);
+  const bool eval_failed = rc == SK_ERR_EVALUATION_FAILED;
+  if (rc && !eval_failed) return rc;
+  if (has_loss_) { apply_loss(b_rc_.p, false); launch_dense_sum(b_cterm_.p, m_, b_scal_.p + 2, s); }
+  else launch_dense_sumsq(b_rc_.p, m_, b_scal_.p + 2, s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 2, b_scal_.p + 2, sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 32, b_dl_scal_.p + 8, sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
+  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
+  int fail = 0;
+  std::memcpy(&fail, h_scal_ + 16, sizeof(int));
+  if (!std::isfinite(h_scal_[32])) return SK_OK;  // invalid step
+  *valid = true;
+  *step_norm = std::sqrt(h_scal_[32]);
   *new_cost = (fail || eval_failed) ? std::numeric_limits<double>::infinity() : 0.5 * h_scal_[2];
   return SK_OK;
 }

@@ -44,6 +44,38 @@ const char* termination_name(int t) {
   return "UNKNOWN";
 }
 
+namespace dogleg {
+bool interpolate(const Scalars& k, double radius, double* a, double* b, double* step_norm, double* model_cost_change) {
+  if (!(k.w_w > 0.0) || !(k.g_g > 0.0) || !std::isfinite(k.p_p) || !std::isfinite(k.m_m) || !std::isfinite(k.w_w)) return false;
+  const double g = std::sqrt(k.g_g), pn = std::sqrt(k.p_p), alpha = k.g_g / k.w_w;
+  if (pn <= radius) {  // the Gauss-Newton step lies inside the region
+    *a = 0.0; *b = 1.0; *step_norm = pn;
+  } else if (alpha * g >= radius) {  // the Cauchy point lies outside: the gradient direction, cut at the boundary
+    *a = radius / g; *b = 0.0; *step_norm = radius;
+  } else {  // where the segment from the Cauchy point to the Gauss-Newton step leaves the region
+    const double a2 = (alpha * g) * (alpha * g), ba = -alpha * k.g_p, bma2 = a2 - 2.0 * ba + k.p_p, c = ba - a2;
+    const double d = std::sqrt(c * c + bma2 * (radius * radius - a2));
+    const double beta = c <= 0.0 ? (d - c) / bma2 : (radius * radius - a2) / (d + c);
+    *a = alpha * (1.0 - beta); *b = beta;
+    *step_norm = std::sqrt(*a * *a * k.g_g - 2.0 * *a * *b * k.g_p + *b * *b * k.p_p);
+  }
+  *model_cost_change = -(*a * k.w_r + *b * k.m_r + 0.5 * (*a * *a * k.w_w + 2.0 * *a * *b * k.w_m + *b * *b * k.m_m));
+  return std::isfinite(*step_norm) && std::isfinite(*model_cost_change);
+}
+}  // namespace dogleg
+
+bool SolverBase::strategy_stat(const std::string& name, double* value) const {
+  if (name == "linear_solves") { *value = (double)n_linear_solves_; return true; }
+  if (name == "dogleg_reused_steps") { *value = (double)n_dl_reused_; return true; }
+  if (name == "dogleg_mu") { *value = dl_mu_; return true; }
+  if (name.rfind("dogleg_", 0) == 0 && dogleg()) {
+    const struct { const char* n; double v; } t[] = {{"dogleg_w_r", dl_k_.w_r}, {"dogleg_m_r", dl_k_.m_r}, {"dogleg_w_w", dl_k_.w_w}, {"dogleg_w_m", dl_k_.w_m},
+      {"dogleg_m_m", dl_k_.m_m}, {"dogleg_g_g", dl_k_.g_g}, {"dogleg_g_p", dl_k_.g_p}, {"dogleg_p_p", dl_k_.p_p}, {"dogleg_a", dl_a_}, {"dogleg_b", dl_b_}};
+    for (const auto& e : t) if (name == e.n) { *value = e.v; return true; }
+  }
+  return false;
+}
+
 SolverBase::~SolverBase() {
   for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
   for (auto& e : ar_pending_) (void)hipEventDestroy(e);
@@ -125,6 +157,12 @@ void SolverBase::log_iteration(int it, double cost_change, double step_norm, dou
 int SolverBase::create() {
   t0_ = std::chrono::steady_clock::now();
   if (opt_.minimizer_type != SK_TRUST_REGION) { set_error("only TRUST_REGION (Levenberg-Marquardt) is implemented"); return SK_ERR_UNSUPPORTED; }
+  if (dogleg()) {
+    if (opt_.dogleg_type != SK_TRADITIONAL_DOGLEG) { set_error("SUBSPACE_DOGLEG is not implemented (not supported: TRADITIONAL_DOGLEG is)"); return SK_ERR_UNSUPPORTED; }
+    if (opt_.world > 1) { set_error("DOGLEG is implemented for one device (not supported in a world of %d ranks)", opt_.world); return SK_ERR_UNSUPPORTED; }
+    if (!supports_dogleg()) { set_error("DOGLEG is implemented for DENSE_SCHUR and for DENSE_QR / DENSE_NORMAL_CHOLESKY over residual blocks (not supported on dense-row problems)"); return SK_ERR_UNSUPPORTED; }
+  }
+  sum_.trust_region_strategy_type = opt_.trust_region_strategy_type;
   int rc = init_device();
   if (rc) return rc;
   rc = setup();
@@ -183,7 +221,8 @@ int SolverBase::step(bool* done) {
       log_iteration(iteration_, 0.0, 0.0, 0.0, 0, 0, now() - t_iter);
       return SK_OK;
     }
-    radius_ /= decrease_factor_; decrease_factor_ *= 2.0;  // StepIsInvalid == StepRejected
+    if (dogleg()) { dl_mu_ *= dogleg::kMuIncreaseFactor; dl_reuse_ = false; }  // DoglegStrategy::StepIsInvalid: the radius stays
+    else { radius_ /= decrease_factor_; decrease_factor_ *= 2.0; }  // StepIsInvalid == StepRejected
     log_iteration(iteration_, 0.0, 0.0, 0.0, 0, 0, now() - t_iter);
     return SK_OK;
   }
@@ -213,13 +252,21 @@ int SolverBase::step(bool* done) {
       terminated_ = true; *done = true; return SK_OK;
     }
     if (rc) return rc;
-    radius_ = radius_ / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3));
-    radius_ = std::min(opt_.max_trust_region_radius, radius_);
-    decrease_factor_ = 2.0;
+    if (dogleg()) {
+      if (rho < dogleg::kDecreaseThreshold) radius_ *= dogleg::kRadiusDecreaseFactor;
+      else if (rho > dogleg::kIncreaseThreshold) radius_ = std::min(opt_.max_trust_region_radius, std::max(radius_, dogleg::kRadiusGrowth * dl_step_norm_));
+      dl_mu_ = std::max(dogleg::kMinMu, dogleg::kMuDecrease * dl_mu_ / dogleg::kMuIncreaseFactor);
+      dl_reuse_ = false;
+    } else {
+      radius_ = radius_ / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3));
+      radius_ = std::min(opt_.max_trust_region_radius, radius_);
+      decrease_factor_ = 2.0;
+    }
     ++n_success_;
     log_iteration(iteration_, cost_change, step_norm, rho, 1, 1, now() - t_iter);
   } else {
-    radius_ /= decrease_factor_; decrease_factor_ *= 2.0;
+    if (dogleg()) { radius_ *= dogleg::kRadiusDecreaseFactor; dl_reuse_ = true; }
+    else { radius_ /= decrease_factor_; decrease_factor_ *= 2.0; }
     ++n_unsuccess_;
     log_iteration(iteration_, cost_change, step_norm, rho, 1, 0, now() - t_iter);
   }
@@ -255,9 +302,10 @@ void Summary::build_reports() {
   snprintf(b, sizeof(b),
            "\nSolver Summary (skeres_amd, MI355X-native Levenberg-Marquardt)\n\n"
            "Parameter blocks            % 12d\nParameters                  % 12d\nResidual blocks             % 12d\nResiduals                   % 12ld\n\n"
-           "Minimizer                        TRUST_REGION\nTrust region strategy     LEVENBERG_MARQUARDT\n\n"
+           "Minimizer                        TRUST_REGION\nTrust region strategy     %19s\n\n"
            "Linear solver          %22s\nDevice                 %s\nGPUs                        % 12d\n",
-           num_parameter_blocks, num_parameters, num_residual_blocks, num_residuals, linear_solver_name(linear_solver_type),
+           num_parameter_blocks, num_parameters, num_residual_blocks, num_residuals,
+           trust_region_strategy_type == SK_DOGLEG ? "DOGLEG (TRADITIONAL)" : "LEVENBERG_MARQUARDT", linear_solver_name(linear_solver_type),
            device_name.c_str(), world);
   f += b;
   if (linear_solver_type_given >= 0 && linear_solver_type_given != linear_solver_type) {

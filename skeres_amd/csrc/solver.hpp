@@ -2,7 +2,8 @@
 // Restates the loop native Ceres [ext] runs behind `ceres.solve`
 // (EX/SimpleBundleAdjuster.scala:152, EX/CurveFitting.scala:127); constants and
 // update rules as published for Ceres 1.x.  Only a
-// handful of scalars cross PCIe per iteration.
+// handful of scalars cross PCIe per iteration.  The trust-region strategy is
+// Levenberg-Marquardt or the traditional dogleg (common.hpp: namespace dogleg).
 #pragma once
 #include <chrono>
 #include <memory>
@@ -27,6 +28,7 @@ class SolverBase {
   virtual double syrk_flops_per_solve() const { return 0.0; }
   virtual double syrk_c_bytes_per_solve() const { return 0.0; }  // C tiles read + written by those launches
   virtual bool stat(const std::string& name, double* value) const { (void)name; (void)value; return false; }  // sk_solver_stat
+  bool dogleg() const { return opt_.trust_region_strategy_type == SK_DOGLEG; }
   // seconds accumulated so far in phase i (the summary's phase_seconds, readable between steps: "phase_seconds_<i>" of sk_solver_stat)
   // (between steps the stream is idle: the all-reduce phase takes in every collective's event pair first)
   double phase_seconds(int i) { if (i == 5) collect_allreduce_time(true); return (i >= 0 && i < 6) ? phase_[i] : 0.0; }
@@ -46,6 +48,7 @@ class SolverBase {
   virtual void accept_candidate() = 0;            // x <- candidate (pointer swap)
   virtual int write_back() = 0;                   // device x -> caller memory
   virtual void describe(Summary* s) = 0;
+  virtual bool supports_dogleg() const { return false; }  // try_step honours dl_reuse_ / dl_mu_ and sets dl_step_norm_
 
   int init_device();
   double now() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0_).count(); }
@@ -68,6 +71,15 @@ class SolverBase {
   double radius_ = 0, decrease_factor_ = 2.0;
   int iteration_ = 0, invalid_ = 0, n_success_ = 0, n_unsuccess_ = 0;
   bool terminated_ = false;
+  // DOGLEG state (common.hpp: namespace dogleg).  try_step sets dl_step_norm_ (the step's norm in the diagonal-scaled space) and
+  // honours dl_reuse_ (the Jacobian has not changed since the last linear solve: interpolate again, solve nothing)
+  double dl_mu_ = dogleg::kMinMu, dl_step_norm_ = 0.0;
+  bool dl_reuse_ = false;
+  long n_linear_solves_ = 0, n_dl_reused_ = 0;  // factorisations enqueued; iterations that re-interpolated (sk_solver_stat)
+  dogleg::Scalars dl_k_;            // the scalars of the last linear solve
+  double dl_a_ = 0.0, dl_b_ = 0.0;  // the coefficients of the last step: a s + b g
+  // "linear_solves", "dogleg_reused_steps", "dogleg_mu"; under DOGLEG also dl_k_, dl_a_, dl_b_ as "dogleg_w_r", ..., "dogleg_b"
+  bool strategy_stat(const std::string& name, double* value) const;
   Summary sum_;
   std::chrono::steady_clock::time_point t0_;
   std::string device_name_;
