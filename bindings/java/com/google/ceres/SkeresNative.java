@@ -80,6 +80,10 @@ public final class SkeresNative {
   public static native int skProblemSetParameterization(long p, long values, long parameterization);
   public static native int skProblemSetParameterBlockConstant(long p, long values);
   public static native int skProblemSetParameterBlockVariable(long p, long values);
+  public static native int skProblemSetParameterLowerBound(long p, long values, int index, double bound);
+  public static native int skProblemSetParameterUpperBound(long p, long values, int index, double bound);
+  public static native double skProblemGetParameterLowerBound(long p, long values, int index);
+  public static native double skProblemGetParameterUpperBound(long p, long values, int index);
   public static native int skProblemNumResidualBlocks(long p);
   public static native int skProblemNumParameterBlocks(long p);
   public static native int skProblemNumParameters(long p);

@@ -279,6 +279,10 @@ SK_JNI(jint, skProblemSetParameterization)(JNIEnv* env, jclass c, jlong p, jlong
 }
 SK_JNI(jint, skProblemSetParameterBlockConstant)(JNIEnv* env, jclass c, jlong p, jlong values) { (void)c; return check(env, sk_problem_set_parameter_block_constant(PTR(sk_problem, p), PTR(double, values))); }
 SK_JNI(jint, skProblemSetParameterBlockVariable)(JNIEnv* env, jclass c, jlong p, jlong values) { (void)c; return check(env, sk_problem_set_parameter_block_variable(PTR(sk_problem, p), PTR(double, values))); }
+SK_JNI(jint, skProblemSetParameterLowerBound)(JNIEnv* env, jclass c, jlong p, jlong values, jint index, jdouble bound) { (void)c; return check(env, sk_problem_set_parameter_lower_bound(PTR(sk_problem, p), PTR(double, values), index, bound)); }
+SK_JNI(jint, skProblemSetParameterUpperBound)(JNIEnv* env, jclass c, jlong p, jlong values, jint index, jdouble bound) { (void)c; return check(env, sk_problem_set_parameter_upper_bound(PTR(sk_problem, p), PTR(double, values), index, bound)); }
+SK_JNI(jdouble, skProblemGetParameterLowerBound)(JNIEnv* env, jclass c, jlong p, jlong values, jint index) { (void)env; (void)c; return sk_problem_get_parameter_lower_bound(PTR(sk_problem, p), PTR(double, values), index); }
+SK_JNI(jdouble, skProblemGetParameterUpperBound)(JNIEnv* env, jclass c, jlong p, jlong values, jint index) { (void)env; (void)c; return sk_problem_get_parameter_upper_bound(PTR(sk_problem, p), PTR(double, values), index); }
 SK_JNI(jint, skProblemNumResidualBlocks)(JNIEnv* env, jclass c, jlong p) { (void)env; (void)c; return sk_problem_num_residual_blocks(PTR(sk_problem, p)); }
 SK_JNI(jint, skProblemNumParameterBlocks)(JNIEnv* env, jclass c, jlong p) { (void)env; (void)c; return sk_problem_num_parameter_blocks(PTR(sk_problem, p)); }
 SK_JNI(jint, skProblemNumParameters)(JNIEnv* env, jclass c, jlong p) { (void)env; (void)c; return sk_problem_num_parameters(PTR(sk_problem, p)); }

@@ -144,6 +144,11 @@ class CeresProblem(options: CeresProblem.Options) {
   def setParameterization(values: DoublePointer, p: LocalParameterization): Unit = SkeresNative.skProblemSetParameterization(handle, values.address, p.handle)
   def setParameterBlockConstant(values: DoublePointer): Unit = SkeresNative.skProblemSetParameterBlockConstant(handle, values.address)
   def setParameterBlockVariable(values: DoublePointer): Unit = SkeresNative.skProblemSetParameterBlockVariable(handle, values.address)
+  // ceres::Problem::SetParameterLowerBound / SetParameterUpperBound and their getters (ceres/problem.h via ceres.i:150)
+  def setParameterLowerBound(values: DoublePointer, index: Int, bound: Double): Unit = SkeresNative.skProblemSetParameterLowerBound(handle, values.address, index, bound)
+  def setParameterUpperBound(values: DoublePointer, index: Int, bound: Double): Unit = SkeresNative.skProblemSetParameterUpperBound(handle, values.address, index, bound)
+  def getParameterLowerBound(values: DoublePointer, index: Int): Double = SkeresNative.skProblemGetParameterLowerBound(handle, values.address, index)
+  def getParameterUpperBound(values: DoublePointer, index: Int): Double = SkeresNative.skProblemGetParameterUpperBound(handle, values.address, index)
   def numResidualBlocks: Int = SkeresNative.skProblemNumResidualBlocks(handle)
   def numParameterBlocks: Int = SkeresNative.skProblemNumParameterBlocks(handle)
   def numParameters: Int = SkeresNative.skProblemNumParameters(handle)

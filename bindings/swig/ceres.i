@@ -50,6 +50,7 @@ void initGoogleLogging(const char* name) { sk_init_logging(name); }
 
 // (sk_options_set_trust_region_strategy_type / sk_options_set_dogleg_type, their two getters and their two enums come through this %include, as the
 // reference's come through ceres/types.h and ceres/solver.h, ceres.i:137,151)
+// (sk_problem_set_parameter_lower_bound / _upper_bound and their getters too, as the reference's come through ceres/problem.h, ceres.i:150)
 %include "skeres_amd.h"
 
 // load the native libraries as the reference's module class does (ceres.i:213-223)

@@ -304,6 +304,30 @@ int sk_problem_add_parameter_block(sk_problem* p, double* values, int size, cons
 int sk_problem_set_parameterization(sk_problem* p, double* values, const sk_local_parameterization* parameterization);
 int sk_problem_set_parameter_block_constant(sk_problem* p, double* values);
 int sk_problem_set_parameter_block_variable(sk_problem* p, double* values);
+/* ceres::Problem::SetParameterLowerBound / SetParameterUpperBound and their getters (ceres/problem.h via ceres.i:150; inherited
+ * by CORE/Problem.scala:16): coordinate `index` of the block at `values` stays inside [lower, upper].  A block that is not part
+ * of the problem (by address), an index outside it and a NaN bound return SK_ERR_INVALID_ARGUMENT (the getters: NaN) with
+ * sk_last_error; -/+ infinity removes a bound, and is what the getters return where nothing is set.
+ *
+ * The solve is Ceres 1.x's constrained trust-region loop, restated from memory like the rest of the minimiser (SURVEY.md
+ * section 8a row a13; the constants: common.hpp, namespace bounds).  x is projected onto the box before the first evaluation
+ * (initial_cost is the projected point's; it is written back even when no step is taken); gradient_max_norm is
+ * max_j |x_j - P(x_j - g_j)|; the linear solve and the model's cost change are those of the unconstrained step delta; the
+ * candidate is P(x + alpha delta), alpha from a backtracking Armijo line search on phi(alpha) = cost(P(x + alpha delta))
+ * (sufficient decrease 1e-4, contraction inside [1e-3, 0.6] alpha, at most 20 contractions, minimum step 1e-9; alpha = 1 when it
+ * fails or delta is no descent direction).  ONE DEPARTURE from Ceres' defaults: the next alpha is the minimiser of the quadratic
+ * through (0, f0, slope g0) and (alpha, phi(alpha)) — function values only — where Ceres interpolates cubically with a Jacobian
+ * at every trial point.  A variable block with lower >= upper at some index, or a constant block outside its bounds, makes
+ * the problem infeasible: the solve ends with SK_FAILURE, the message names block and index, the parameters stay untouched.
+ * Refused with SK_ERR_UNSUPPORTED when the solver is created: bounds with DOGLEG; in a world of more than one rank; on
+ * dense-row problems; with host-evaluated (director) residual blocks under DENSE_SCHUR; on a block that carries a quaternion or
+ * homogeneous-vector parameterization.  Constant blocks, identity and subset parameterizations and recorded functors are
+ * taken.  Under bounds the iteration is enqueued launch by launch (sk_solver_stat "graph_replay" is 0); a problem without a
+ * finite bound runs exactly what it ran before. */
+int sk_problem_set_parameter_lower_bound(sk_problem* p, double* values, int index, double bound);
+int sk_problem_set_parameter_upper_bound(sk_problem* p, double* values, int index, double bound);
+double sk_problem_get_parameter_lower_bound(const sk_problem* p, const double* values, int index);
+double sk_problem_get_parameter_upper_bound(const sk_problem* p, const double* values, int index);
 int sk_problem_num_residual_blocks(const sk_problem* p);   /* Problem::NumResidualBlocks */
 int sk_problem_num_parameter_blocks(const sk_problem* p);  /* Problem::NumParameterBlocks */
 int sk_problem_num_parameters(const sk_problem* p);        /* Problem::NumParameters */
@@ -476,7 +500,9 @@ const char* sk_summary_brief_report(const sk_summary* s);    /* Summary.briefRep
 const char* sk_summary_full_report(const sk_summary* s);     /* Summary.fullReport(); EX/SimpleBundleAdjuster.scala:154 */
 /* Per-iteration log (what minimizer_progress_to_stdout prints). field:
  * 0 cost, 1 cost_change, 2 gradient_max_norm, 3 step_norm, 4 relative_decrease,
- * 5 trust_region_radius, 6 step_is_valid, 7 step_is_successful */
+ * 5 trust_region_radius, 6 step_is_valid, 7 step_is_successful,
+ * 8 step_size (the line search's alpha under parameter bounds; 1 without), 9 line_search_evaluations (candidate costs
+ * evaluated in the iteration: the ls_iter column; 1 without bounds) */
 int sk_summary_num_logged_iterations(const sk_summary* s);
 double sk_summary_iteration_field(const sk_summary* s, int iteration, int field);
 /* Device time per phase, seconds, summed over the solve (HIP events on the
@@ -548,6 +574,9 @@ int sk_solver_distribution(const sk_solver* s, double* allreduce_seconds, double
  *   "dogleg_w_r" "dogleg_m_r" "dogleg_w_w" "dogleg_w_m" "dogleg_m_m" "dogleg_g_g" "dogleg_g_p" "dogleg_p_p" "dogleg_a" "dogleg_b"
  *                           DOGLEG: the scalars of the last linear solve (w = J s, m = J g over the observations; g-hat and
  *                           the Gauss-Newton step p in the diagonal-scaled space) and the coefficients of the last step a s + b g
+ *   "bounded_coordinates"   coordinates with a finite bound (sk_problem_set_parameter_lower_bound / _upper_bound)
+ *   "active_bounds"         coordinates of the current x that sit exactly on a bound
+ *   "line_search_evaluations" candidate costs evaluated by the line search under bounds, since the solver was created
  * dense rows (DENSE_NORMAL_CHOLESKY over one parameter block):
  *   "jtj_flops_algorithmic" m n (n + 1): SURVEY.md section 8(d)'s figure for J^T J (sk_solver_syrk_flops_per_solve counts
  *                           the padded 128 x 128 tiles the launch computes) */

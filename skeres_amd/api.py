@@ -62,6 +62,10 @@ _SIGS = {
     "sk_problem_add_parameter_block": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_void_p]),
     "sk_problem_set_parameterization": (C.c_int, [C.c_void_p, _dp, C.c_void_p]),
     "sk_problem_set_parameter_block_constant": (C.c_int, [C.c_void_p, _dp]),
+    "sk_problem_set_parameter_lower_bound": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_double]),
+    "sk_problem_set_parameter_upper_bound": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_double]),
+    "sk_problem_get_parameter_lower_bound": (C.c_double, [C.c_void_p, _dp, C.c_int]),
+    "sk_problem_get_parameter_upper_bound": (C.c_double, [C.c_void_p, _dp, C.c_int]),
     "sk_problem_set_parameter_block_variable": (C.c_int, [C.c_void_p, _dp]),
     "sk_loss_soft_l_one": (C.c_void_p, [C.c_double]),
     "sk_loss_cauchy": (C.c_void_p, [C.c_double]),
@@ -1018,6 +1022,31 @@ class Problem:
             raise ValueError(lib().sk_last_error().decode())
         _check(rc)
 
+    # ceres::Problem::SetParameterLowerBound / SetParameterUpperBound and their getters (ceres/problem.h via ceres.i:150)
+    def setParameterLowerBound(self, values, index, bound):
+        rc = lib().sk_problem_set_parameter_lower_bound(self._h, values.cast(), int(index), float(bound))
+        if rc == 1:
+            raise ValueError(lib().sk_last_error().decode())
+        _check(rc)
+
+    def setParameterUpperBound(self, values, index, bound):
+        rc = lib().sk_problem_set_parameter_upper_bound(self._h, values.cast(), int(index), float(bound))
+        if rc == 1:
+            raise ValueError(lib().sk_last_error().decode())
+        _check(rc)
+
+    def getParameterLowerBound(self, values, index):
+        v = lib().sk_problem_get_parameter_lower_bound(self._h, values.cast(), int(index))
+        if v != v:
+            raise ValueError(lib().sk_last_error().decode())
+        return v
+
+    def getParameterUpperBound(self, values, index):
+        v = lib().sk_problem_get_parameter_upper_bound(self._h, values.cast(), int(index))
+        if v != v:
+            raise ValueError(lib().sk_last_error().decode())
+        return v
+
     def addResidualBlocks(self, functor_id, consts, loss, base, offsets):
         """Bulk form of the loop at EX/SimpleBundleAdjuster.scala:139-145.
         ``base`` is a DoubleArray, ``offsets`` an int array [n, num_blocks] of
@@ -1250,7 +1279,7 @@ class Solver:
 
         def iterations(self):
             names = ["cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease",
-                     "trust_region_radius", "step_is_valid", "step_is_successful"]
+                     "trust_region_radius", "step_is_valid", "step_is_successful", "step_size", "line_search_evaluations"]
             return [{nm: lib().sk_summary_iteration_field(self._h, i, k) for k, nm in enumerate(names)}
                     for i in range(lib().sk_summary_num_logged_iterations(self._h))]
 

@@ -1355,4 +1355,100 @@ void launch_bal_dogleg_combine(const BalDev& d, const DoglegDev& q, double a, do
   launch_final_reduce(q.partial + 8 * (size_t)q.stride, q.stride, g, 1, 0, q.scal + 8, s);
 }
 
+// ---------------------------------------------------------------------------
+// F. Parameter bounds (common.hpp: namespace bounds).  Streaming passes over the [cameras | points] vector, one coordinate per
+// lane (adjacent lanes read adjacent doubles of every array), workgroup results to rows of q.partial that a final reduction
+// folds in a fixed order: no atomics, reruns are bitwise equal.
+// ---------------------------------------------------------------------------
+__global__ void box_project_kernel(double* x, const double* __restrict__ lo, const double* __restrict__ hi, int n) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) x[j] = fmin(fmax(x[j], lo[j]), hi[j]);
+}
+
+// rows 3-5 of q.partial: max |x_j - P(x_j - g_j)| with g = gs / scale, the gradient in the caller's coordinates (a coordinate
+// held constant has no gradient entry), sum x_j^2, and how many x_j sit exactly on a bound
+__global__ __launch_bounds__(kBlock) void bounded_grad_max_xnorm_kernel(const double* __restrict__ gs, const double* __restrict__ scale, const double* __restrict__ x,
+                                                                        int n, BoundsDev q) {
+  double m = 0.0;
+  double acc[2] = {0.0, 0.0};
+  for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
+    const double xj = x[j], lo = q.lo[j], hi = q.hi[j];
+    if (scale[j] != 0.0) m = fmax(m, fabs(xj - fmin(fmax(xj - gs[j] / scale[j], lo), hi)));
+    acc[0] += xj * xj;
+    acc[1] += (xj == lo || xj == hi) ? 1.0 : 0.0;
+  }
+  __shared__ double shm[kBlock / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+  if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < kBlock / 64; ++i) m = fmax(m, shm[i]);
+    q.partial[3 * (size_t)q.stride + blockIdx.x] = m;
+  }
+  block_sum<2>(acc, q.partial + 4 * (size_t)q.stride, q.stride);
+}
+
+// g0 = g . delta = sum gs_j step_j (the scaling cancels) and max |delta_j|, delta = step * scale: rows 1 and 2.  A pseudo-camera's
+// slots of step_c hold the retained points' steps: they are counted as points (step_p), not here.
+__global__ __launch_bounds__(kBlock) void bal_directional_derivative_kernel(BalDev d, BoundsDev q) {
+  double m = 0.0;
+  double acc[1] = {0.0};
+  const int nc = 9 * d.C, n = nc + 3 * d.P;
+  for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
+    if (j < nc && d.pseudo && d.pseudo[j / 9]) continue;
+    const double st = d.step_c[j];
+    acc[0] += d.gs_c[j] * st;
+    m = fmax(m, fabs(st * d.scale_c[j]));
+  }
+  __shared__ double shm[kBlock / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+  if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < kBlock / 64; ++i) m = fmax(m, shm[i]);
+    q.partial[2 * (size_t)q.stride + blockIdx.x] = m;
+  }
+  block_sum<1>(acc, q.partial + q.stride, q.stride);
+}
+
+// The candidate of one trial: x_new = P(x + (alpha step) scale) for cameras, eliminated points and retained points (whose step
+// bal_kept_step_kernel left in step_p), and |x - x_new|^2 as bal_cam_step_kernel, bal_point_backsub_kernel and
+// bal_kept_step_kernel account for it: every parameter once, a retained point as a point, a pseudo-camera's inert slots not at
+// all.  A coordinate held constant has scale 0 and keeps its bits (set-up checked that it lies inside its bounds).
+__global__ __launch_bounds__(kBlock) void bal_bounded_candidate_kernel(BalDev d, BoundsDev q, double alpha) {
+  double acc[1] = {0.0};
+  const int nc = 9 * d.C, n = nc + 3 * d.P;
+  for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
+    const double xo = d.xc[j];
+    double xn = xo;
+    if (!(j < nc && d.pseudo && d.pseudo[j / 9])) xn = fmin(fmax(xo + (alpha * d.step_c[j]) * d.scale_c[j], q.lo[j]), q.hi[j]);  // (alpha = 1: the expression, and the bits, of bal_cam_step_kernel)
+    d.xc_new[j] = xn;
+    const double df = xo - xn;
+    acc[0] += df * df;
+  }
+  block_sum<1>(acc, q.partial, q.stride);
+}
+
+int bounds_partial_stride(int n) { return grid_for(n); }
+void launch_box_project(double* x, const double* lo, const double* hi, int n, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(box_project_kernel, dim3((n + 255) / 256), dim3(256), 0, s, x, lo, hi, n);
+}
+void launch_bounded_grad_max_xnorm(const double* gs, const double* scale, const double* x, int n, const BoundsDev& q, hipStream_t s) {
+  const int g = grid_for(n);
+  hipLaunchKernelGGL(bounded_grad_max_xnorm_kernel, dim3(g), dim3(kBlock), 0, s, gs, scale, x, n, q);
+  launch_final_reduce(q.partial + 3 * (size_t)q.stride, q.stride, g, 3, 1, q.scal + 3, s);
+}
+void launch_bal_directional_derivative(const BalDev& d, const BoundsDev& q, hipStream_t s) {
+  const int g = grid_for(9 * d.C + 3 * d.P);
+  hipLaunchKernelGGL(bal_directional_derivative_kernel, dim3(g), dim3(kBlock), 0, s, d, q);
+  launch_final_reduce(q.partial + q.stride, q.stride, g, 2, 2, q.scal + 1, s);
+}
+void launch_bal_bounded_candidate(const BalDev& d, const BoundsDev& q, double alpha, hipStream_t s) {
+  const int g = grid_for(9 * d.C + 3 * d.P);
+  hipLaunchKernelGGL(bal_bounded_candidate_kernel, dim3(g), dim3(kBlock), 0, s, d, q, alpha);
+  launch_final_reduce(q.partial, q.stride, g, 1, 0, q.scal, s);
+}
+
 }  // namespace sk

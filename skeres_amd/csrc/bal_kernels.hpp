@@ -161,4 +161,17 @@ void launch_bal_dogleg_products(const BalDev& d, const DoglegDev& q, hipStream_t
 void launch_dogleg_reduce_scalars(const DoglegDev& q, hipStream_t s);                  // rows 0-7 -> scal[0..7], fixed order
 void launch_bal_dogleg_combine(const BalDev& d, const DoglegDev& q, double a, double b, hipStream_t s);  // x_new = x + (a s + b g) scale; scal[8]
 
+// Parameter bounds (bal_kernels.hip, section F; common.hpp: namespace bounds).  lo / hi: the box over the whole parameter vector
+// in the layout of xc / xp ([cameras | points]; -/+ infinity where nothing is set, and on padding and pseudo-camera coordinates);
+// partial: 6 rows of `stride` partial results (zeroed once); scal[0]: |x - x_new|^2 of the last candidate, scal[1]: g . delta,
+// scal[2]: max_j |delta_j|, scal[3]: max_j |x_j - P(x_j - g_j)|, scal[4]: |x|^2, scal[5]: coordinates of x on a bound.
+struct BoundsDev { const double* lo; const double* hi; double* partial; int stride; double* scal; };
+int bounds_partial_stride(int n);
+void launch_box_project(double* x, const double* lo, const double* hi, int n, hipStream_t s);  // x_j <- min(max(x_j, lo_j), hi_j)
+// the bounded form of launch_grad_max_xnorm over n coordinates: scal[3..5]
+void launch_bounded_grad_max_xnorm(const double* gs, const double* scale, const double* x, int n, const BoundsDev& q, hipStream_t s);
+void launch_bal_directional_derivative(const BalDev& d, const BoundsDev& q, hipStream_t s);  // after launch_bal_backsub: scal[1], scal[2]
+// xc_new / xp_new = clamp(x + alpha step scale) for cameras, eliminated and retained points; scal[0]
+void launch_bal_bounded_candidate(const BalDev& d, const BoundsDev& q, double alpha, hipStream_t s);
+
 }  // namespace sk

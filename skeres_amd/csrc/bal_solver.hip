@@ -151,6 +151,18 @@ class BalSolver : public SolverBase {
   int try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm);
   int dogleg_candidate(double a, double b, double* new_cost, double* step_norm, bool* failed);
   bool supports_dogleg() const override { return true; }
+  // Parameter bounds: try_step_once, told so by bounded_, forms the candidate P(x + delta) behind the back-substitution and leaves
+  // g . delta and max |delta_j|; the line search's further trials are bounded_trial (the candidate launch, the cost kernel, the reduce)
+  int try_step_bounded(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm);
+  int bounded_trial(double alpha, double* cost, double* step_norm) override;
+  const char* refuses_bounds() const override {
+    for (int f : problem_->rb_functor)
+      if (f == SK_FUNCTOR_HOST_CALLBACK) return "parameter bounds with host-evaluated (director) residual blocks under DENSE_SCHUR are not supported";
+    return nullptr;
+  }
+  int upload_bounds();
+  BoundsDev bd_{};
+  DevBuf<double> b_bd_box_, b_bd_partial_, b_bd_scal_;
   DoglegDev dl_{};
   DevBuf<double> b_dl_vec_, b_dl_partial_, b_dl_scal_;
   void accept_candidate() override { std::swap(d_.xc, d_.xc_new); std::swap(d_.xp, d_.xp_new); parity_ ^= 1; }
@@ -385,6 +397,7 @@ int BalSolver::setup() {
   if ((rc = allocate_fronts(layout_fronts(fi)))) return rc;
   stage("fronts, zero pass, tables");
   if ((rc = bind_device_view(ls))) return rc;
+  if (bounded_ && (rc = upload_bounds())) return rc;
   if ((rc = agree_with_ranks())) return rc;
   stage("device view, the ranks' agreement");
   return SK_OK;
@@ -404,7 +417,7 @@ int BalSolver::init_queues() {
         if (p.rb_functor[b] == SK_FUNCTOR_HOST_CALLBACK) { set_error("DOGLEG with host-evaluated (director) residual blocks under DENSE_SCHUR is not supported"); return SK_ERR_UNSUPPORTED; }
     }
     // (DOGLEG: the captured sequences are Levenberg-Marquardt's — launch by launch)
-    graph_mode_ = npad_ / 128 <= 8 && !opt_.allreduce && !host_or_tape && opt_.dissection != SK_DISSECTION_ON && dev_knobs().dissect_at < 0 && opt_.graph_replay && !dogleg();
+    graph_mode_ = npad_ / 128 <= 8 && !opt_.allreduce && !host_or_tape && opt_.dissection != SK_DISSECTION_ON && dev_knobs().dissect_at < 0 && opt_.graph_replay && !dogleg() && !bounded_;
     if (graph_mode_) opt_.lookahead = false;  // one stream: the whole iteration is one in-order launch sequence
   }
   chol_ctx_.resident = chol_ctx_b_.resident = opt_.resident_kernels;
@@ -842,6 +855,30 @@ int BalSolver::bind_device_view(const LocalStructure& ls) {
   return SK_OK;
 }
 
+// Parameter bounds: the box in the layout of x, and x projected onto it before the first evaluation.
+int BalSolver::upload_bounds() {
+  const Problem& p = *problem_;
+  hipStream_t s = stream_;
+  const size_t nc = 9 * (size_t)C_, nx = nc + 3 * (size_t)P_;
+  const double inf = std::numeric_limits<double>::infinity();
+  std::vector<double> box(2 * nx);
+  std::fill(box.begin(), box.begin() + (long)nx, -inf); std::fill(box.begin() + (long)nx, box.end(), inf);
+  auto fill = [&](int block, size_t off, int size) {
+    for (int k = 0; k < size; ++k) { box[off + k] = p.lower_bound((size_t)block, k); box[nx + off + k] = p.upper_bound((size_t)block, k); }
+  };
+  for (int i = 0; i < C_; ++i) if (cam_block_[i] >= 0) fill(cam_block_[i], 9 * (size_t)i, cam_size_);
+  for (int q = 0; q < P_; ++q) fill(pt_block_[local_pt_[q]], nc + 3 * (size_t)q, pt_size_);
+  SK_HIP_TRY(b_bd_box_.upload(box, s));
+  bd_.stride = bounds_partial_stride((int)nx);
+  SK_HIP_TRY(b_bd_partial_.alloc(6 * (size_t)bd_.stride)); SK_HIP_TRY(b_bd_partial_.zero(s));
+  SK_HIP_TRY(b_bd_scal_.alloc(8)); SK_HIP_TRY(b_bd_scal_.zero(s));
+  bd_.lo = b_bd_box_.p; bd_.hi = b_bd_box_.p + nx; bd_.partial = b_bd_partial_.p; bd_.scal = b_bd_scal_.p;
+  // (a coordinate held constant lies inside its bounds — SolverBase::check_bounds — so the projection leaves it alone)
+  launch_box_project(d_.xc, bd_.lo, bd_.hi, (int)nx, s);
+  SK_HIP_TRY(hipStreamSynchronize(s));  // (box is pageable)
+  return SK_OK;
+}
+
 int BalSolver::agree_with_ranks() {
   if (!opt_.allreduce) return SK_OK;
   // every rank derived the camera order and the envelope for itself (from rank-invariant data): they must be the same
@@ -977,6 +1014,7 @@ int BalSolver::evaluate_with_jacobian(bool first) {
     // one process: cameras and points as ONE vector ([cameras | points] in every buffer), and the three reductions — sum r^2,
     // max |g|, |x|^2 — in one launch (round 4: five launches of ~6 us each became two)
     const int g = launch_grad_max_xnorm(b_gs_.p, b_scale_.p, d_.xc, (int)(nc + np), b_partial_.p + (size_t)partial_stride_, partial_stride_, s);
+    // (under bounds the gradient test is the projected gradient's: below, in a launch of its own — this one's maximum is not read)
     // (slots 2 and 3, the points' share in a world of ranks, stay zero: it is inside the cameras' slots here)
     ReduceRows rows;
     rows.n = 3;
@@ -1002,6 +1040,10 @@ int BalSolver::evaluate_with_jacobian(bool first) {
   launch_final_reduce(b_partial_.p + 2 * (size_t)partial_stride_, partial_stride_, np_own ? gp : 0, 2, 1, b_scal_.p + 2, s);
   }
   SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (bounded_) {  // max |x - P(x - g)|, |x|^2 and the active bounds in one launch (one device: the whole vector)
+    kt_.begin("bounded_grad_max_xnorm", s); launch_bounded_grad_max_xnorm(b_gs_.p, b_scale_.p, d_.xc, (int)(nc + np), bd_, s); kt_.end("bounded_grad_max_xnorm", s);
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 40, bd_.scal + 3, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
   }
   if (graph) {
     if (!replay) { capture.release(); int rc = finish_capture(s, &g_eval_[parity_]); if (rc) return rc; if (!graph_mode_) return evaluate_with_jacobian(first); }
@@ -1025,6 +1067,7 @@ int BalSolver::evaluate_with_jacobian(bool first) {
   cost_ = 0.5 * loc[0];
   gmax_ = segmented_ ? loc[1] : std::max(gmax_c, loc[1]);
   xnorm_ = std::sqrt((segmented_ ? 0.0 : x2_c) + loc[2]);
+  if (bounded_) { gmax_ = h_scal_[40]; active_bounds_ = (long)h_scal_[42]; }
   if (!std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
   return SK_OK;
 }
@@ -1034,6 +1077,7 @@ int BalSolver::evaluate_with_jacobian(bool first) {
 // and factored again, launch by launch, in the same iteration — the trajectory does not change.
 int BalSolver::try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
   if (dogleg()) return try_step_dogleg(radius, valid, mcc, new_cost, step_norm);
+  if (bounded_) return try_step_bounded(radius, valid, mcc, new_cost, step_norm);
   bool chain_lost = false;
   int rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
   if (rc == SK_OK && chain_lost) rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
@@ -1169,6 +1213,11 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
     launch_dogleg_reduce_scalars(dl_, s);
     SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, dl_.scal, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
   }
+  if (bounded_) {  // g . delta and max |delta_j| of the unconstrained step; the candidate becomes P(x + delta) (counted with the back-substitution)
+    kt_.begin("bal_directional_derivative", s); launch_bal_directional_derivative(d_, bd_, s); kt_.end("bal_directional_derivative", s);
+    kt_.begin("bal_bounded_candidate", s); launch_bal_bounded_candidate(d_, bd_, 1.0, s); kt_.end("bal_bounded_candidate", s);
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 44, bd_.scal, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
   if (!graph) SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
   if (!dogleg()) {  // (DOGLEG: the candidate is formed and evaluated by dogleg_candidate)
   kt_.begin("bal_eval_cost", s);
@@ -1227,7 +1276,38 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
   *valid = true;
   *mcc = -loc[1];
   *new_cost = candidate_failed ? std::numeric_limits<double>::max() : 0.5 * loc[0];
-  *step_norm = std::sqrt(step_sq);
+  *step_norm = std::sqrt(bounded_ ? h_scal_[44] : step_sq);
+  return SK_OK;
+}
+
+// Parameter bounds (common.hpp: namespace bounds).  The linear solve and the model's cost change are the unconstrained
+// step's at this radius; the candidate is P(x + alpha delta), alpha from the line search.  phi(1) came with the solve.
+int BalSolver::try_step_bounded(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
+  bool chain_lost = false;
+  int rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
+  if (rc == SK_OK && chain_lost) rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
+  if (rc || !*valid) return rc;
+  return line_search(h_scal_[45], h_scal_[46], new_cost, step_norm);
+}
+
+int BalSolver::bounded_trial(double alpha, double* cost, double* step_norm) {
+  hipStream_t s = stream_;
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
+  kt_.begin("bal_bounded_candidate", s); launch_bal_bounded_candidate(d_, bd_, alpha, s); kt_.end("bal_bounded_candidate", s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
+  kt_.begin("bal_eval_cost", s);
+  if (tape_mode_) launch_bal_eval_cost_tape(d_, tape_dev_, s); else launch_bal_eval_cost(d_, s);  // (its model term: not used here)
+  kt_.end("bal_eval_cost", s);
+  launch_final_reduce(b_partial_.p, partial_stride_, bal_partial_blocks(N_), 1, 0, b_scal_.p, s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 44, bd_.scal, sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
+  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
+  *cost = 0.5 * h_scal_[0];
+  *step_norm = std::sqrt(h_scal_[44]);
   return SK_OK;
 }
 

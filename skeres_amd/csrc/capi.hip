@@ -442,6 +442,35 @@ static int set_block_constant(sk_problem* p, double* values, char constant) {
 int sk_problem_set_parameter_block_constant(sk_problem* p, double* values) { return set_block_constant(p, values, 1); }
 int sk_problem_set_parameter_block_variable(sk_problem* p, double* values) { return set_block_constant(p, values, 0); }
 
+// ceres::Problem::SetParameterLowerBound / SetParameterUpperBound / GetParameterLowerBound / GetParameterUpperBound
+// (ceres/problem.h via ceres.i:150)
+static int bound_block(const Problem& P, const double* values, int index) {
+  auto it = P.block_of.find(const_cast<double*>(values));
+  if (it == P.block_of.end()) { set_error("parameter block %p is not part of the problem", (const void*)values); return -1; }
+  if (index < 0 || index >= P.block_size[it->second]) { set_error("index %d is outside the parameter block of size %d", index, P.block_size[it->second]); return -1; }
+  return it->second;
+}
+static int set_bound(sk_problem* p, double* values, int index, double bound, bool upper) {
+  SK_GUARD_BEGIN
+  if (!p) { set_error("null problem"); return SK_ERR_INVALID_ARGUMENT; }
+  if (bound != bound) { set_error("a parameter bound must not be NaN"); return SK_ERR_INVALID_ARGUMENT; }
+  const int id = bound_block(p->p, values, index);
+  if (id < 0) return SK_ERR_INVALID_ARGUMENT;
+  p->p.set_bound((size_t)id, index, bound, upper);
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_problem_set_parameter_lower_bound(sk_problem* p, double* values, int index, double bound) { return set_bound(p, values, index, bound, false); }
+int sk_problem_set_parameter_upper_bound(sk_problem* p, double* values, int index, double bound) { return set_bound(p, values, index, bound, true); }
+static double get_bound(const sk_problem* p, const double* values, int index, bool upper) {
+  if (!p) { set_error("null problem"); return NAN; }
+  const int id = bound_block(p->p, values, index);
+  if (id < 0) return NAN;
+  return upper ? p->p.upper_bound((size_t)id, index) : p->p.lower_bound((size_t)id, index);
+}
+double sk_problem_get_parameter_lower_bound(const sk_problem* p, const double* values, int index) { return get_bound(p, values, index, false); }
+double sk_problem_get_parameter_upper_bound(const sk_problem* p, const double* values, int index) { return get_bound(p, values, index, true); }
+
 int sk_problem_add_residual_block(sk_problem* p, const sk_cost_function* cost, const sk_loss_function* loss, double* const* parameter_blocks,
                                   int num_parameter_blocks, sk_residual_block_id* id_out) {
   SK_GUARD_BEGIN
@@ -664,6 +693,7 @@ double sk_summary_iteration_field(const sk_summary* s, int it, int field) {
   switch (field) {
     case 0: return L.cost; case 1: return L.cost_change; case 2: return L.gradient_max_norm; case 3: return L.step_norm;
     case 4: return L.relative_decrease; case 5: return L.trust_region_radius; case 6: return L.step_is_valid; case 7: return L.step_is_successful;
+    case 8: return L.step_size; case 9: return L.line_search_evaluations;
   }
   return NAN;
 }

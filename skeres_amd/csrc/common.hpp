@@ -115,11 +115,24 @@ struct Scalars {
 bool interpolate(const Scalars& k, double radius, double* a, double* b, double* step_norm, double* model_cost_change);
 }  // namespace dogleg
 
+// Parameter bounds: Ceres 1.x's constrained trust-region loop (projected steps with a backtracking Armijo line search), recalled,
+// not pinned (like SURVEY.md §8a row a13), so the constants live here and nowhere else.  The interpolation is the one departure
+// from Ceres' defaults: quadratic, from function values only (Ceres: CUBIC, which needs a Jacobian at every trial point).
+namespace bounds {
+constexpr double kSufficientDecrease = 1e-4;
+constexpr double kMaxStepContraction = 1e-3, kMinStepContraction = 0.6;  // the next alpha lies inside [1e-3 alpha, 0.6 alpha]
+constexpr int kMaxNumIterations = 20;                                     // contractions
+constexpr double kMinStepSize = 1e-9;                                     // of alpha max_j |delta_j|
+constexpr double kBisection = 0.5;                                        // after a trial whose cost is not finite
+}  // namespace bounds
+
 struct IterationLog {
   int iteration = 0;
   double cost = 0, cost_change = 0, gradient_max_norm = 0, step_norm = 0, relative_decrease = 0,
          trust_region_radius = 0, iter_time = 0, total_time = 0;
   int step_is_valid = 1, step_is_successful = 1;
+  double step_size = 1.0;           // the line search's alpha under parameter bounds
+  int line_search_evaluations = 1;  // candidate costs evaluated in the iteration
 };
 
 struct Summary {

@@ -548,4 +548,78 @@ void launch_dense_qr(const double* J, const double* r, const double* D, int m, i
   hipLaunchKernelGGL(dense_qr_solve_kernel, dim3(1), dim3(256), 0, s, A, b, m + n, n, y, ok);
 }
 
+// ---- parameter bounds (common.hpp: namespace bounds): the dense forms of bal_kernels.hip section F, one workgroup each ----
+__global__ __launch_bounds__(256) void dense_bounded_gmax_kernel(const double* gs, const double* scale, const double* x, const int* ambient, const double* lo,
+                                                                 const double* hi, int n, int ng, double* out) {
+  __shared__ double shm[256], shs[256], sha[256];
+  double mx = 0.0, s = 0.0, a = 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) {
+    const double g = gs[j] / scale[j];
+    const int i = ambient[j];
+    mx = fmax(mx, i < 0 ? fabs(g) : fabs(x[i] - fmin(fmax(x[i] - g, lo[i]), hi[i])));
+  }
+  for (int i = threadIdx.x; i < ng; i += 256) { s += x[i] * x[i]; a += (x[i] == lo[i] || x[i] == hi[i]) ? 1.0 : 0.0; }
+  shm[threadIdx.x] = mx; shs[threadIdx.x] = s; sha[threadIdx.x] = a;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) { shm[threadIdx.x] = fmax(shm[threadIdx.x], shm[threadIdx.x + w]); shs[threadIdx.x] += shs[threadIdx.x + w]; sha[threadIdx.x] += sha[threadIdx.x + w]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = shm[0]; out[1] = shs[0]; out[2] = sha[0]; }
+}
+__global__ __launch_bounds__(256) void dense_directional_derivative_kernel(const double* gs, const double* step, const double* scale, int n, double* out) {
+  __shared__ double shs[256], shm[256];
+  double s = 0.0, mx = 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) { s += gs[j] * step[j]; mx = fmax(mx, fabs(step[j] * scale[j])); }
+  shs[threadIdx.x] = s; shm[threadIdx.x] = mx;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) { shs[threadIdx.x] += shs[threadIdx.x + w]; shm[threadIdx.x] = fmax(shm[threadIdx.x], shm[threadIdx.x + w]); }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = shs[0]; out[1] = shm[0]; }
+}
+// n: coordinates (blocks == nullptr) or parameter blocks; the tangent form clamps after Plus
+__global__ __launch_bounds__(256) void dense_bounded_candidate_kernel(const double* step, const double* scale, const double* x, double alpha, const ParamBlock* blocks,
+                                                                      int nblocks, const double* lo, const double* hi, double* x_new, int n, double* out) {
+  __shared__ double sh[256];
+  double s = 0.0;
+  if (blocks) {
+    for (int b = threadIdx.x; b < nblocks; b += 256) {
+      const ParamBlock pb = blocks[b];
+      double delta[kParamMaxSize], xp[kParamMaxSize];
+      for (int c = 0; c < pb.local_size; ++c) delta[c] = (alpha * step[pb.local_off + c]) * scale[pb.local_off + c];
+      param_plus(pb, x + pb.global_off, delta, xp);
+      for (int i = 0; i < pb.global_size; ++i) {
+        const int k = pb.global_off + i;
+        const double xn = fmin(fmax(xp[i], lo[k]), hi[k]);
+        x_new[k] = xn;
+        const double d = x[k] - xn;
+        s += d * d;
+      }
+    }
+  } else {
+    for (int j = threadIdx.x; j < n; j += 256) {
+      const double xn = fmin(fmax(x[j] + (alpha * step[j]) * scale[j], lo[j]), hi[j]);  // (alpha = 1: the expression of dense_step_kernel)
+      x_new[j] = xn;
+      const double d = x[j] - xn;
+      s += d * d;
+    }
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) { if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
+  if (threadIdx.x == 0) out[0] = sh[0];
+}
+void launch_dense_bounded_gmax(const double* gs, const double* scale, const double* x, const int* ambient, const double* lo, const double* hi, int n, int ng, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(dense_bounded_gmax_kernel, dim3(1), dim3(256), 0, s, gs, scale, x, ambient, lo, hi, n, ng, out);
+}
+void launch_dense_directional_derivative(const double* gs, const double* step, const double* scale, int n, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(dense_directional_derivative_kernel, dim3(1), dim3(256), 0, s, gs, step, scale, n, out);
+}
+void launch_dense_bounded_candidate(const double* step, const double* scale, const double* x, double alpha, const ParamBlock* blocks, int nblocks,
+                                    const double* lo, const double* hi, double* x_new, int n, double* out, hipStream_t s) {
+  hipLaunchKernelGGL(dense_bounded_candidate_kernel, dim3(1), dim3(256), 0, s, step, scale, x, alpha, blocks, nblocks, lo, hi, x_new, n, out);
+}
+
 }  // namespace sk

@@ -31,6 +31,10 @@ class DenseSolver : public SolverBase {
   int try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm);
   int enqueue_linear_solve(double radius);  // D from the radius, the normal equations or the QR, y; records kEvAssemble and kEvChol
   bool supports_dogleg() const override { return true; }
+  // Parameter bounds: try_step forms P(x + delta) (tangent_: the clamp follows Plus) and runs the line search; every further trial is
+  // bounded_trial (the candidate launch, the cost evaluation)
+  const char* refuses_bounds() const override { return nullptr; }
+  int bounded_trial(double alpha, double* cost, double* step_norm) override;
   void accept_candidate() override { std::swap(x_, x_new_); }
   int write_back() override;
   void describe(Summary* s) override {
@@ -61,6 +65,8 @@ class DenseSolver : public SolverBase {
 
  private:
   DevBuf<double> b_dl_vec_, b_dl_scal_;  // DOGLEG: [s | g]; the eight scalars and |x - x_new|^2
+  DevBuf<double> b_bd_box_, b_bd_scal_;  // bounds: [lo | hi] over x; |x - x_new|^2, g . delta, max |delta_j|, then the gradient test's three
+  DevBuf<int> b_bd_ambient_;             // tangent coordinate -> coordinate of x (dense_kernels.hpp)
   int evaluate(const double* x_dev, bool jac);
   int host_callbacks(const double* x_dev, bool jac);
 
@@ -180,6 +186,21 @@ int DenseSolver::setup() {
   SK_HIP_TRY(b_fail_.alloc(1)); SK_HIP_TRY(b_fail_.zero(s)); SK_HIP_TRY(b_info_.alloc(1)); SK_HIP_TRY(b_info_.zero(s)); SK_HIP_TRY(b_ok_.alloc(1));
   SK_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_scal_), 64 * sizeof(double), hipHostMallocDefault));
   if (dogleg()) { SK_HIP_TRY(b_dl_vec_.alloc(2 * (size_t)n_)); SK_HIP_TRY(b_dl_scal_.alloc(16)); SK_HIP_TRY(b_dl_scal_.zero(s)); }
+  if (bounded_) {  // the box in the layout of x, and x projected onto it before the first evaluation
+    std::vector<double> box(2 * (size_t)ng_);
+    for (size_t b = 0; b < p.block_size.size(); ++b)
+      for (int i = 0; i < p.block_size[b]; ++i) { box[block_off_[b] + i] = p.lower_bound(b, i); box[(size_t)ng_ + block_off_[b] + i] = p.upper_bound(b, i); }
+    std::vector<int> ambient(n_, -1);
+    if (!tangent_) for (int j = 0; j < n_; ++j) ambient[j] = j;
+    for (const ParamBlock& pb : pblocks) {
+      if (pb.type != kParamIdentity && pb.type != kParamSubset) continue;
+      for (int i = 0, l = 0; i < pb.global_size; ++i)
+        if (pb.type == kParamIdentity || !((pb.constant_mask >> i) & 1u)) ambient[pb.local_off + l++] = pb.global_off + i;
+    }
+    SK_HIP_TRY(b_bd_box_.upload(box, s)); SK_HIP_TRY(b_bd_ambient_.upload(ambient, s));
+    SK_HIP_TRY(b_bd_scal_.alloc(8)); SK_HIP_TRY(b_bd_scal_.zero(s));
+    launch_box_project(x_, b_bd_box_.p, b_bd_box_.p + ng_, ng_, s);
+  }
   SK_HIP_TRY(hipStreamSynchronize(s));
   return SK_OK;
 }
@@ -266,6 +287,10 @@ int DenseSolver::evaluate_with_jacobian(bool first) {
   launch_dense_gmax(b_gs_.p, b_scale_.p, x_, n_, b_scal_.p + 1, s);
   if (tangent_) launch_dense_sumsq(x_, ng_, b_scal_.p + 2, s);  // |x|^2 over the ambient vector
   SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (bounded_) {  // the gradient test is the projected gradient's
+    launch_dense_bounded_gmax(b_gs_.p, b_scale_.p, x_, b_bd_ambient_.p, b_bd_box_.p, b_bd_box_.p + ng_, n_, ng_, b_bd_scal_.p + 3, s);
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 40, b_bd_scal_.p + 3, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
   SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
   SK_HIP_TRY(hipEventRecord(ev_[kEvJac], s));
   SK_HIP_TRY(hipStreamSynchronize(s));
@@ -273,6 +298,7 @@ int DenseSolver::evaluate_with_jacobian(bool first) {
   if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvJac]) == hipSuccess) phase_[0] += 1e-3 * ms;
   int fail = 0; std::memcpy(&fail, h_scal_ + 16, sizeof(int));
   cost_ = 0.5 * h_scal_[0]; gmax_ = h_scal_[1]; xnorm_ = std::sqrt(h_scal_[2]);
+  if (bounded_) { gmax_ = h_scal_[40]; active_bounds_ = (long)h_scal_[42]; }
   if (fail || !std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
   return SK_OK;
 }
@@ -309,6 +335,11 @@ int DenseSolver::try_step(double radius, bool* valid, double* mcc, double* new_c
   if (tangent_) launch_dense_plus(b_y_.p, b_scale_.p, x_, b_step_.p, x_new_, b_pblocks_.p, num_pblocks_, b_scal_.p, s);
   else launch_dense_step(b_y_.p, b_scale_.p, x_, b_step_.p, x_new_, n_, b_scal_.p, s);
   launch_dense_model(b_J_.p, b_r_.p, b_step_.p, m_, n_, b_scal_.p + 1, s);
+  if (bounded_) {  // g . delta and max |delta_j| of the unconstrained step; the candidate becomes P(x + delta)
+    launch_dense_directional_derivative(b_gs_.p, b_step_.p, b_scale_.p, n_, b_bd_scal_.p + 1, s);
+    launch_dense_bounded_candidate(b_step_.p, b_scale_.p, x_, 1.0, tangent_ ? b_pblocks_.p : nullptr, num_pblocks_, b_bd_box_.p, b_bd_box_.p + ng_, x_new_, n_, b_scal_.p, s);
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 44, b_bd_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
   SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
   rc = evaluate(x_new_, false);
   const bool eval_failed = rc == SK_ERR_EVALUATION_FAILED;
@@ -333,6 +364,33 @@ int DenseSolver::try_step(double radius, bool* valid, double* mcc, double* new_c
   *step_norm = std::sqrt(h_scal_[0]);
   *mcc = -h_scal_[1];
   *new_cost = (fail || eval_failed) ? std::numeric_limits<double>::infinity() : 0.5 * h_scal_[2];
+  if (bounded_) return line_search(h_scal_[45], h_scal_[46], new_cost, step_norm);
+  return SK_OK;
+}
+
+// One trial of the line search under bounds: the candidate P(Plus(x, alpha delta)), its cost, |x - candidate|.
+int DenseSolver::bounded_trial(double alpha, double* cost, double* step_norm) {
+  hipStream_t s = stream_;
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
+  SK_HIP_TRY(hipMemsetAsync(b_fail_.p, 0, sizeof(int), s));
+  launch_dense_bounded_candidate(b_step_.p, b_scale_.p, x_, alpha, tangent_ ? b_pblocks_.p : nullptr, num_pblocks_, b_bd_box_.p, b_bd_box_.p + ng_, x_new_, n_, b_scal_.p, s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
+  int rc = evaluate(x_new_, false);
+  const bool eval_failed = rc == SK_ERR_EVALUATION_FAILED;
+  if (rc && !eval_failed) return rc;
+  if (has_loss_) { apply_loss(b_rc_.p, false); launch_dense_sum(b_cterm_.p, m_, b_scal_.p + 2, s); }
+  else launch_dense_sumsq(b_rc_.p, m_, b_scal_.p + 2, s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
+  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
+  int fail = 0;
+  std::memcpy(&fail, h_scal_ + 16, sizeof(int));
+  *step_norm = std::sqrt(h_scal_[0]);
+  *cost = (fail || eval_failed) ? std::numeric_limits<double>::infinity() : 0.5 * h_scal_[2];
   return SK_OK;
 }
 

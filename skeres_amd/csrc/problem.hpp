@@ -2,7 +2,9 @@
 // reduced system (bal_plan.cpp) reads a Problem and is compiled without the device headers.  The device side of each type
 // lives where it did: loss.hpp, parameterization.hpp, tape.hpp (which include this file).
 #pragma once
+#include <cmath>
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <string>
 #include <unordered_map>
@@ -108,6 +110,26 @@ struct Problem {  // CeresProblem; parameter blocks identified by pointer value
   bool has_parameterization() const {
     for (size_t b = 0; b < block_ptr.size(); ++b)
       if ((b < block_param.size() && block_param[b] >= 0) || (b < block_constant.size() && block_constant[b])) return true;
+    return false;
+  }
+  // Problem::SetParameterLowerBound / SetParameterUpperBound (ceres/problem.h via ceres.i:150): per block, allocated when a bound
+  // is first set (block_size entries, -/+ infinity where nothing is set); a problem without bounds carries two empty vectors
+  std::vector<std::vector<double>> block_lower, block_upper;
+  double lower_bound(size_t b, int i) const { return b < block_lower.size() && !block_lower[b].empty() ? block_lower[b][i] : -std::numeric_limits<double>::infinity(); }
+  double upper_bound(size_t b, int i) const { return b < block_upper.size() && !block_upper[b].empty() ? block_upper[b][i] : std::numeric_limits<double>::infinity(); }
+  void set_bound(size_t b, int i, double v, bool upper) {
+    std::vector<std::vector<double>>& t = upper ? block_upper : block_lower;
+    if (t.size() <= b) { if (std::isinf(v)) return; t.resize(block_ptr.size()); }
+    if (t[b].empty()) { if (std::isinf(v)) return; t[b].assign(block_size[b], upper ? std::numeric_limits<double>::infinity() : -std::numeric_limits<double>::infinity()); }
+    t[b][i] = v;
+  }
+  bool block_has_bounds(size_t b) const {
+    for (int i = 0; i < block_size[b]; ++i) if (std::isfinite(lower_bound(b, i)) || std::isfinite(upper_bound(b, i))) return true;
+    return false;
+  }
+  bool has_bounds() const {  // some coordinate has a finite bound
+    if (block_lower.empty() && block_upper.empty()) return false;
+    for (size_t b = 0; b < block_ptr.size(); ++b) if (block_has_bounds(b)) return true;
     return false;
   }
   long num_residuals = 0;

@@ -65,6 +65,9 @@ bool interpolate(const Scalars& k, double radius, double* a, double* b, double* 
 }  // namespace dogleg
 
 bool SolverBase::strategy_stat(const std::string& name, double* value) const {
+  if (name == "bounded_coordinates") { *value = (double)bounded_coordinates_; return true; }
+  if (name == "active_bounds") { *value = (double)active_bounds_; return true; }
+  if (name == "line_search_evaluations") { *value = (double)n_ls_evals_; return true; }
   if (name == "linear_solves") { *value = (double)n_linear_solves_; return true; }
   if (name == "dogleg_reused_steps") { *value = (double)n_dl_reused_; return true; }
   if (name == "dogleg_mu") { *value = dl_mu_; return true; }
@@ -145,11 +148,12 @@ void SolverBase::log_iteration(int it, double cost_change, double step_norm, dou
   L.iteration = it; L.cost = cost_; L.cost_change = cost_change; L.gradient_max_norm = gmax_;
   L.step_norm = step_norm; L.relative_decrease = rho; L.trust_region_radius = radius_;
   L.step_is_valid = valid; L.step_is_successful = success; L.iter_time = iter_time; L.total_time = now();
+  L.step_size = ls_alpha_; L.line_search_evaluations = ls_evals_;
   sum_.iterations.push_back(L);
   if (opt_.progress_to_stdout && opt_.rank == 0) {
     if (it == 0) printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius  ls_iter  iter_time  total_time\n");
     printf("%4d % 8e   % 3.2e   % 3.2e  % 3.2e  % 3.2e % 3.2e     % 4d   % 3.2e   % 3.2e\n", it, L.cost, L.cost_change,
-           L.gradient_max_norm, L.step_norm, L.relative_decrease, L.trust_region_radius, 1, L.iter_time, L.total_time);
+           L.gradient_max_norm, L.step_norm, L.relative_decrease, L.trust_region_radius, L.line_search_evaluations, L.iter_time, L.total_time);
     fflush(stdout);
   }
 }
@@ -163,7 +167,10 @@ int SolverBase::create() {
     if (!supports_dogleg()) { set_error("DOGLEG is implemented for DENSE_SCHUR and for DENSE_QR / DENSE_NORMAL_CHOLESKY over residual blocks (not supported on dense-row problems)"); return SK_ERR_UNSUPPORTED; }
   }
   sum_.trust_region_strategy_type = opt_.trust_region_strategy_type;
-  int rc = init_device();
+  int rc = check_bounds();
+  if (rc) return rc;
+  if (infeasible_) return SK_OK;
+  rc = init_device();
   if (rc) return rc;
   rc = setup();
   if (rc) return rc;
@@ -181,6 +188,74 @@ int SolverBase::create() {
   iteration_ = 0;
   log_iteration(0, 0.0, 0.0, 0.0, 1, 1, now());
   sum_.termination_type = SK_NO_CONVERGENCE;
+  return SK_OK;
+}
+
+// Parameter bounds, before anything touches the device: what is refused, and whether the box is feasible (Ceres:
+// Problem::IsFeasible in the preprocessor — "lower >= upper" for a variable block, a constant block outside its bounds).
+int SolverBase::check_bounds() {
+  const Problem& p = *problem_;
+  bounded_ = p.has_bounds();
+  if (!bounded_) return SK_OK;
+  if (dogleg()) { set_error("parameter bounds with DOGLEG are not supported (LEVENBERG_MARQUARDT takes them)"); return SK_ERR_UNSUPPORTED; }
+  if (opt_.world > 1) { set_error("parameter bounds are implemented for one device (not supported in a world of %d ranks)", opt_.world); return SK_ERR_UNSUPPORTED; }
+  if (const char* why = refuses_bounds()) { set_error("%s", why); return SK_ERR_UNSUPPORTED; }
+  char msg[256];
+  for (size_t b = 0; b < p.block_ptr.size(); ++b) {
+    if (!p.block_has_bounds(b)) continue;
+    const int pi = b < p.block_param.size() ? p.block_param[b] : -1;
+    if (pi >= 0 && (p.params[pi].type == kParamQuaternion || p.params[pi].type == kParamHomogeneousVector)) {
+      set_error("parameter bounds on block %d, which carries a quaternion or homogeneous-vector parameterization, are not supported", (int)b);
+      return SK_ERR_UNSUPPORTED;
+    }
+    const bool constant = b < p.block_constant.size() && p.block_constant[b];
+    for (int i = 0; i < p.block_size[b]; ++i) {
+      const double lo = p.lower_bound(b, i), hi = p.upper_bound(b, i);
+      const bool held = constant || (pi >= 0 && p.params[pi].type == kParamSubset && ((p.params[pi].constant_mask >> i) & 1u));
+      if (std::isfinite(lo) || std::isfinite(hi)) ++bounded_coordinates_;
+      msg[0] = 0;
+      if (held) {
+        const double v = p.block_ptr[b][i];
+        if (!(v >= lo && v <= hi)) snprintf(msg, sizeof(msg), "Infeasible problem: parameter block %d, index %d is constant at %g outside its bounds [%g, %g].", (int)b, i, v, lo, hi);
+      } else if (lo >= hi) {
+        snprintf(msg, sizeof(msg), "Infeasible problem: parameter block %d, index %d has lower bound %g >= upper bound %g.", (int)b, i, lo, hi);
+      }
+      if (msg[0]) { sum_.termination_type = SK_FAILURE; sum_.message = msg; terminated_ = true; infeasible_ = true; return SK_OK; }
+    }
+  }
+  return SK_OK;
+}
+
+// The line search of an iteration under bounds (common.hpp: namespace bounds) on phi(alpha) = cost(P(x + alpha delta)), f0 = cost_.
+// In: *cost = phi(1) and *step_norm of the candidate try_step has formed.  Out: those of the alpha that was kept (ls_alpha_), the
+// candidate buffers holding its point.  A search that fails keeps alpha = 1, as Ceres leaves delta alone.
+int SolverBase::line_search(double g0, double max_delta, double* cost, double* step_norm) {
+  ls_alpha_ = 1.0; ls_evals_ = 1; ++n_ls_evals_;
+  if (!(g0 < 0.0) || !std::isfinite(g0)) return SK_OK;
+  const double f0 = cost_;
+  double alpha = 1.0, phi = *cost, norm = *step_norm;
+  bool found = false;
+  for (int contractions = 0;; ++contractions) {
+    if (std::isfinite(phi) && phi <= f0 + bounds::kSufficientDecrease * alpha * g0) { found = true; break; }
+    if (contractions == bounds::kMaxNumIterations) break;
+    double next = bounds::kBisection * alpha;
+    if (std::isfinite(phi)) {
+      next = -g0 * alpha * alpha / (2.0 * (phi - f0 - g0 * alpha));
+      next = std::min(std::max(next, bounds::kMaxStepContraction * alpha), bounds::kMinStepContraction * alpha);
+    }
+    if (next * max_delta < bounds::kMinStepSize) break;
+    alpha = next;
+    int rc = bounded_trial(alpha, &phi, &norm);
+    if (rc) return rc;
+    ++ls_evals_; ++n_ls_evals_;
+  }
+  if (!found && alpha != 1.0) {  // back to the full step: its point into the candidate buffers again
+    alpha = 1.0;
+    int rc = bounded_trial(alpha, &phi, &norm);
+    if (rc) return rc;
+    ++ls_evals_; ++n_ls_evals_;
+  }
+  ls_alpha_ = alpha; *cost = phi; *step_norm = norm;
   return SK_OK;
 }
 
@@ -206,6 +281,7 @@ int SolverBase::step(bool* done) {
   }
   const double t_iter = now();
   ++iteration_;
+  ls_alpha_ = 1.0; ls_evals_ = 1;
   bool valid = false;
   double mcc = 0.0, new_cost = 0.0, step_norm = 0.0;
   int rc = try_step(radius_, &valid, &mcc, &new_cost, &step_norm);
@@ -274,7 +350,7 @@ int SolverBase::step(bool* done) {
 }
 
 int SolverBase::finish(Summary* s) {
-  int rc = write_back();
+  int rc = infeasible_ ? SK_OK : write_back();  // (an infeasible problem: nothing was set up, the caller's parameters stay untouched)
   if (rc) return rc;
   collect_allreduce_time(true);
   sum_.final_cost = cost_;

@@ -4,6 +4,11 @@
 // update rules as published for Ceres 1.x.  Only a
 // handful of scalars cross PCIe per iteration.  The trust-region strategy is
 // Levenberg-Marquardt or the traditional dogleg (common.hpp: namespace dogleg).
+// Parameter bounds (Problem::SetParameterLowerBound / SetParameterUpperBound): Ceres 1.x's constrained loop, restated from
+// memory like the rest — x projected onto the box at iteration 0, the projected-gradient norm, the unconstrained step delta
+// and its model, and a backtracking Armijo line search on cost(P(x + alpha delta)) (common.hpp: namespace bounds).  One
+// deliberate departure from Ceres' defaults: the line search interpolates quadratically from function values, not cubically
+// with a Jacobian at every trial point.
 #pragma once
 #include <chrono>
 #include <memory>
@@ -49,6 +54,18 @@ class SolverBase {
   virtual int write_back() = 0;                   // device x -> caller memory
   virtual void describe(Summary* s) = 0;
   virtual bool supports_dogleg() const { return false; }  // try_step honours dl_reuse_ / dl_mu_ and sets dl_step_norm_
+  // Parameter bounds (bounded_: the problem has a finite bound).  refuses_bounds: why this solver cannot take this problem's
+  // bounds, or nullptr.  try_step then forms the candidate P(x + delta), leaves g0 = g . delta and max_j |delta_j| to
+  // line_search, which asks for every further trial through bounded_trial (candidate of alpha, its cost, |x - candidate|).
+  virtual const char* refuses_bounds() const { return "parameter bounds are implemented for DENSE_SCHUR and for DENSE_QR / DENSE_NORMAL_CHOLESKY over residual blocks (not supported on dense-row problems)"; }
+  virtual int bounded_trial(double alpha, double* cost, double* step_norm) { (void)alpha; (void)cost; (void)step_norm; return SK_ERR_UNSUPPORTED; }
+  int line_search(double g0, double max_delta, double* cost, double* step_norm);
+  int check_bounds();  // create(): the refusals, the feasibility of the box
+  bool bounded_ = false, infeasible_ = false;
+  double ls_alpha_ = 1.0;          // of the last iteration
+  int ls_evals_ = 1;
+  long n_ls_evals_ = 0;            // since create ("line_search_evaluations")
+  long bounded_coordinates_ = 0, active_bounds_ = 0;
 
   int init_device();
   double now() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0_).count(); }
@@ -78,6 +95,7 @@ class SolverBase {
   long n_linear_solves_ = 0, n_dl_reused_ = 0;  // factorisations enqueued; iterations that re-interpolated (sk_solver_stat)
   dogleg::Scalars dl_k_;            // the scalars of the last linear solve
   double dl_a_ = 0.0, dl_b_ = 0.0;  // the coefficients of the last step: a s + b g
+  // "bounded_coordinates", "active_bounds", "line_search_evaluations";
   // "linear_solves", "dogleg_reused_steps", "dogleg_mu"; under DOGLEG also dl_k_, dl_a_, dl_b_ as "dogleg_w_r", ..., "dogleg_b"
   bool strategy_stat(const std::string& name, double* value) const;
   Summary sum_;
