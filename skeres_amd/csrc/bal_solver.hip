@@ -6,12 +6,8 @@
 // are partitioned over ranks, cameras are replicated, and the reduced system
 // is summed with one all-reduce per linear solve.
 #include <algorithm>
-#include <atomic>
-#include <map>
-#include <thread>
 #include <cmath>
 #include <limits>
-#include <numeric>
 
 #include "bal_kernels.hpp"
 #include "bal_plan.hpp"
@@ -144,17 +140,21 @@ class BalSolver : public SolverBase {
  protected:
   int setup() override;
   int evaluate_with_jacobian(bool first) override;
-  int try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) override;
-  int try_step_once(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm, bool* chain_lost);
-  // DOGLEG: the linear solve is try_step_once with radius = 1 / mu, which then stops behind the back-substitution and leaves the
-  // eight scalars (DoglegDev::scal); the candidate of this radius — and of every smaller one after a rejection — is dogleg_candidate
-  int try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm);
-  int dogleg_candidate(double a, double b, double* new_cost, double* step_norm, bool* failed);
-  bool supports_dogleg() const override { return true; }
-  // Parameter bounds: try_step_once, told so by bounded_, forms the candidate P(x + delta) behind the back-substitution and leaves
-  // g . delta and max |delta_j|; the line search's further trials are bounded_trial (the candidate launch, the cost kernel, the reduce)
-  int try_step_bounded(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm);
+  // SolverBase's three stepping virtuals.  linear_solve: solve_once, and once more launch by launch after a time-out of the resident
+  // panel chain.  The two trials form their candidate and share trial_cost.
+  int linear_solve(double radius, LinearSolve* out) override;
+  int dogleg_trial(double a, double b, double* cost, double* step_norm) override;
   int bounded_trial(double alpha, double* cost, double* step_norm) override;
+  bool supports_dogleg() const override { return true; }
+  // One linear solve with what the strategy needs behind its back-substitution: capture or replay, the one synchronisation, the
+  // decoding.  What it enqueues is the four stages below, in this order; each records the event that ends its phase.
+  int solve_once(double radius, LinearSolve* out, bool* chain_lost);
+  struct Backsolve { int resident; bool zero_after; };  // decided once per step, for every front: the resident launch; whether it zeroes what it reads
+  int enqueue_schur_assembly(const Backsolve& bs, bool graph);
+  int enqueue_factor_backsolve(const Backsolve& bs, bool graph);
+  int enqueue_point_backsub(bool graph);
+  int enqueue_candidate_cost(int rows, bool* failed);  // rows: 1 the sum of squares, 2 the model term too
+  int trial_cost(const double* step_sq_dev, int step_sq_slot, double* cost, double* step_norm);
   const char* refuses_bounds() const override {
     for (int f : problem_->rb_functor)
       if (f == SK_FUNCTOR_HOST_CALLBACK) return "parameter bounds with host-evaluated (director) residual blocks under DENSE_SCHUR are not supported";
@@ -189,7 +189,8 @@ class BalSolver : public SolverBase {
   int gather_rank_scalars_signed(double* vals, int K);
   bool rank_table_on_device(int K) const;
   int enqueue_rank_table(int mode, int K);
-  int fold_rank_table(double* vals, int K, const int* ops);
+  int fold_rank_table(const double* table, double* vals, int K, const int* ops);
+  int exchange_rank_table(const double* vals, int K, std::vector<double>* table);
 
   int C_ = 0, P_total_ = 0, P_ = 0, N_ = 0;   // cameras, all points, local points, local observations
   int res_size_ = 2, cam_size_ = 9, pt_size_ = 3;  // the problem's own (r; c, q) (bal_block_shape): padded to (2; 9, 3) inside
@@ -200,7 +201,7 @@ class BalSolver : public SolverBase {
   DevBuf<LossNode> b_loss_nodes_;
   DevBuf<int> b_loss_of_obs_;
   DevBuf<int> b_cam_, b_pt_, b_pt_start_, b_cam_start_, b_cam_obs_, b_obs_slot_, b_seg_start_, b_seg_row_, b_seg_col_, b_pair_row_, b_pair_col_, b_short_segs_, b_long_segs_;
-  int *fail_p_ = nullptr, *info_p_ = nullptr;  // device flags: slots 14 and 15 of b_scal_ (one reset, one copy back with the scalars)
+  int *fail_p_ = nullptr, *info_p_ = nullptr;  // device flags: kFail and kInfo of b_scal_ (one reset, one copy back with the scalars)
   DevBuf<double> b_obs_, b_xc_, b_xp_, b_xc_new_, b_xp_new_, b_scale_, b_colsq_, b_gs_, b_step_, b_y_,
       b_r_, b_F_, b_Fcam_, b_E_, b_W_, b_rt_, b_M_, b_q_, b_S_, b_Linv_, b_partial_, b_scal_, b_small_;
   std::vector<int> env_last_;  // block envelope of S (cholesky_factor); empty = dense
@@ -299,7 +300,31 @@ class BalSolver : public SolverBase {
     stage_last_ = now;
   }
   CholeskyContext chol_ctx_;
-  double* h_scal_ = nullptr;  // pinned
+  // The scalars that cross PCIe.  b_scal_ (device, kDevSlots doubles) is copied back to the same slots of h_scal_ (pinned) as one block:
+  // [kEvalFirst, kEvalLast] by an evaluation, [kStepFirst, kStepLast] by a step.  The device numbers are the ones the kernels know
+  // (bal_pack_rank_scalars_kernel reads them; launch_final_reduce and launch_bal_backsub write runs of two).  Behind the block, h_scal_
+  // holds regions that may all be live in one iteration, so none overlaps another.
+  enum Slot {
+    kGradMaxCam = 0, kXSqCam, kGradMaxPt, kXSqPt, kSumSq,  // evaluation: max |g| and |x|^2 over the cameras (one process: over everything), over this rank's points; sum r^2
+    kEvalFirst = kGradMaxCam, kEvalLast = kSumSq,
+    kCandSumSq = 0, kModel,                  // step: the candidate's sum r^2, the model term
+    kStepSqCam = 8, kStepSqPt,               // ... |delta_c|^2, |delta_p|^2
+    kRadiusDev = 12,                         // device only: the radius a replayed graph reads (BalDev::lm_radius_dev)
+    kFail = 14, kInfo,                       // two int flags, one double slot each (host_flag): BalDev::fail_flag, the factorisation's info
+    kStepFirst = kCandSumSq, kStepLast = kInfo,
+    kDevSlots = kStepLast + 1,
+    kRadius = kDevSlots,                     // h_scal_ only from here.  The radius: the captured host-to-device copy reads this address at every replay
+    kDogleg,                                 // mirror of DoglegDev::scal (DoglegScal)
+    kBounds = kDogleg + kDlScalCount,        // mirror of BoundsDev::scal (BoundsScal)
+    kRankTable = kBounds + kBdScalCount,     // the table of the ranks' scalars formed on the device: world * K <= kRankTableSlots doubles
+    kRankTableSlots = 24,
+    kHostSlots = kRankTable + kRankTableSlots
+  };
+  static_assert(kEvalLast < kStepSqCam && kModel < kStepSqCam && kStepSqPt < kRadiusDev && kRadiusDev < kFail, "b_scal_'s slots are distinct");
+  static_assert(kStepLast < kRadius && kRadius < kDogleg && kDogleg + kDlScalCount <= kBounds && kBounds + kBdScalCount <= kRankTable, "h_scal_'s regions do not overlap");
+  double* h_scal_ = nullptr;  // pinned, kHostSlots doubles
+  int host_flag(int slot) const { int v = 0; std::memcpy(&v, h_scal_ + slot, sizeof(int)); return v; }
+  double* rank_table_dev() const { return b_small_.p + 2 * 9 * (size_t)C_ + 6 * retained_pts_.size() + 64; }  // (b_small_: behind the sums of an evaluation)
   int partial_stride_ = 0;
   // The envelope of S has to be zero again before the next assembly (the factor overwrote it).  Round 4: the back-substitution
   // does it — every block of L below the diagonal is read exactly once there, by the owner workgroup of its column, which
@@ -766,9 +791,9 @@ int BalSolver::allocate_fronts(const FrontLayout& lay) {
   if (dissected_ && !segmented_) { SK_HIP_TRY(b_mapB_.upload(lay.mapB, s)); mapB_involution_ = lay.mapB_involution; }
   partial_stride_ = std::max(std::max(std::max(bal_partial_blocks(N_), bal_point_blocks(P_) + 1), (9 * C_ + 255) / 256), 256) + bal_partial_blocks((int)host_obs_.size());  // (+ 1: the retained points' slot)
   SK_HIP_TRY(b_partial_.alloc(4 * (size_t)partial_stride_));
-  SK_HIP_TRY(b_scal_.alloc(16)); SK_HIP_TRY(b_scal_.zero(s)); SK_HIP_TRY(b_small_.alloc(2 * 9 * (size_t)C_ + 6 * retained_pts_.size() + 64 + 16 * (size_t)opt_.world));
-  fail_p_ = reinterpret_cast<int*>(b_scal_.p + 14); info_p_ = reinterpret_cast<int*>(b_scal_.p + 15);
-  SK_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_scal_), 64 * sizeof(double), hipHostMallocDefault));
+  SK_HIP_TRY(b_scal_.alloc(kDevSlots)); SK_HIP_TRY(b_scal_.zero(s)); SK_HIP_TRY(b_small_.alloc(2 * 9 * (size_t)C_ + 6 * retained_pts_.size() + 64 + 16 * (size_t)opt_.world));
+  fail_p_ = reinterpret_cast<int*>(b_scal_.p + kFail); info_p_ = reinterpret_cast<int*>(b_scal_.p + kInfo);
+  SK_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_scal_), kHostSlots * sizeof(double), hipHostMallocDefault));
   if (dogleg()) {
     BalDev shape{}; shape.C = C_; shape.P = P_; shape.N = N_;
     const size_t nx = 9 * (size_t)C_ + 3 * (size_t)P_;
@@ -899,22 +924,20 @@ int BalSolver::agree_with_ranks() {
   if (off[0] > 0.0) cholesky_disable_chain(&chol_ctx_);
   return SK_OK;
 }
-// max over ranks of each value (values of either sign)
-// The same table formed on the DEVICE (bal_pack_rank_scalars_kernel), summed and copied to pinned host memory behind whatever the
+// The table of the ranks' scalars formed on the DEVICE (bal_pack_rank_scalars_kernel), summed and copied to pinned host memory behind whatever the
 // stream holds — the caller synchronises once and folds.  For worlds whose table fits the pinned scalars' spare room.
-bool BalSolver::rank_table_on_device(int K) const { return opt_.allreduce != nullptr && opt_.world > 1 && opt_.world * K <= 24; }
+bool BalSolver::rank_table_on_device(int K) const { return opt_.allreduce != nullptr && opt_.world > 1 && opt_.world * K <= kRankTableSlots; }
 int BalSolver::enqueue_rank_table(int mode, int K) {
-  double* dev = b_small_.p + 2 * 9 * (size_t)C_ + 6 * retained_pts_.size() + 64;
+  double* dev = rank_table_dev();
   launch_bal_pack_rank_scalars(b_scal_.p, dev, opt_.rank, opt_.world, mode, segmented_, stream_);
   int rc = allreduce(dev, (size_t)opt_.world * K);
   if (rc) return rc;
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 36, dev, (size_t)opt_.world * K * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kRankTable, dev, (size_t)opt_.world * K * sizeof(double), hipMemcpyDeviceToHost, stream_));
   return SK_OK;
 }
-int BalSolver::fold_rank_table(double* vals, int K, const int* ops) {
+int BalSolver::fold_rank_table(const double* table, double* vals, int K, const int* ops) {
   const int W = opt_.world;
-  const double* table = h_scal_ + 36;
-  const int fold = fold_world_ > 0 ? std::min(fold_world_, W) : W;
+  const int fold = fold_world_ > 0 ? std::min(fold_world_, W) : W;  // (segmented: ranks beyond the first segments_ are replicas)
   for (int k = 0; k < K; ++k) {
     double a = 0.0;
     for (int r = 0; r < fold; ++r) a = ops[k] ? std::max(a, table[(size_t)r * K + k]) : a + table[(size_t)r * K + k];
@@ -922,45 +945,37 @@ int BalSolver::fold_rank_table(double* vals, int K, const int* ops) {
   }
   return SK_OK;
 }
-int BalSolver::gather_rank_scalars_signed(double* vals, int K) {
-  const int W = opt_.world;
-  std::vector<double> table((size_t)W * K, 0.0);
-  for (int k = 0; k < K; ++k) table[(size_t)opt_.rank * K + k] = vals[k];
-  double* dev = b_small_.p + 2 * 9 * (size_t)C_ + 6 * retained_pts_.size() + 64;
-  SK_HIP_TRY(hipMemcpyAsync(dev, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-  int rc = allreduce(dev, table.size());
+// The same table from host values: every rank writes its K values into its own row of a world x K table of zeros, the table is
+// sum-reduced and brought back (one synchronisation).
+int BalSolver::exchange_rank_table(const double* vals, int K, std::vector<double>* table) {
+  table->assign((size_t)opt_.world * K, 0.0);
+  for (int k = 0; k < K; ++k) (*table)[(size_t)opt_.rank * K + k] = vals[k];
+  double* dev = rank_table_dev();
+  SK_HIP_TRY(hipMemcpyAsync(dev, table->data(), table->size() * sizeof(double), hipMemcpyHostToDevice, stream_));
+  int rc = allreduce(dev, table->size());
   if (rc) return rc;
-  SK_HIP_TRY(hipMemcpyAsync(table.data(), dev, table.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
+  SK_HIP_TRY(hipMemcpyAsync(table->data(), dev, table->size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
   SK_HIP_TRY(hipStreamSynchronize(stream_));
+  return SK_OK;
+}
+// max over ranks of each value (values of either sign)
+int BalSolver::gather_rank_scalars_signed(double* vals, int K) {
+  std::vector<double> table;
+  int rc = exchange_rank_table(vals, K, &table);
+  if (rc) return rc;
   for (int k = 0; k < K; ++k) {
     double a = table[k];
-    for (int r = 1; r < W; ++r) a = std::max(a, table[(size_t)r * K + k]);
+    for (int r = 1; r < opt_.world; ++r) a = std::max(a, table[(size_t)r * K + k]);
     vals[k] = a;
   }
   return SK_OK;
 }
-
-// Combine per-rank scalars: every rank writes its K values into its own slot of
-// a world x K table, the table is sum-reduced, then each rank folds the slots
-// in rank order (identical result on every rank; ops: 0 sum, 1 max).
+// Combine per-rank scalars: each rank folds the rows in rank order (identical result on every rank; ops: 0 sum, 1 max).
 int BalSolver::gather_rank_scalars(double* vals, int K, const int* ops) {
   if (!opt_.allreduce) return SK_OK;
-  const int W = opt_.world;
-  std::vector<double> table((size_t)W * K, 0.0);
-  for (int k = 0; k < K; ++k) table[(size_t)opt_.rank * K + k] = vals[k];
-  double* dev = b_small_.p + 2 * 9 * (size_t)C_ + 6 * retained_pts_.size() + 64;
-  SK_HIP_TRY(hipMemcpyAsync(dev, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, stream_));
-  int rc = allreduce(dev, table.size());
-  if (rc) return rc;
-  SK_HIP_TRY(hipMemcpyAsync(table.data(), dev, table.size() * sizeof(double), hipMemcpyDeviceToHost, stream_));
-  SK_HIP_TRY(hipStreamSynchronize(stream_));
-  const int fold = fold_world_ > 0 ? std::min(fold_world_, W) : W;  // (segmented: ranks beyond the first two are replicas)
-  for (int k = 0; k < K; ++k) {
-    double a = 0.0;
-    for (int r = 0; r < fold; ++r) a = ops[k] ? std::max(a, table[(size_t)r * K + k]) : a + table[(size_t)r * K + k];
-    vals[k] = a;
-  }
-  return SK_OK;
+  std::vector<double> table;
+  int rc = exchange_rank_table(vals, K, &table);
+  return rc ? rc : fold_rank_table(table.data(), vals, K, ops);
 }
 
 int BalSolver::evaluate_with_jacobian(bool first) {
@@ -1009,21 +1024,21 @@ int BalSolver::evaluate_with_jacobian(bool first) {
     launch_bal_cam_records(d_, s);  // F changed under the records
     launch_apply_scale_to_reductions(b_colsq_.p, b_gs_.p, b_scale_.p, (int)(nc + np), s);
   }
-  // scalars: sum r^2 (slot 4) ; gradient max-norm and |x|^2 (cameras once, points local)
+  // scalars: sum r^2 ; gradient max-norm and |x|^2 (cameras once, points local)
   if (!opt_.allreduce) {
     // one process: cameras and points as ONE vector ([cameras | points] in every buffer), and the three reductions — sum r^2,
     // max |g|, |x|^2 — in one launch (round 4: five launches of ~6 us each became two)
     const int g = launch_grad_max_xnorm(b_gs_.p, b_scale_.p, d_.xc, (int)(nc + np), b_partial_.p + (size_t)partial_stride_, partial_stride_, s);
     // (under bounds the gradient test is the projected gradient's: below, in a launch of its own — this one's maximum is not read)
-    // (slots 2 and 3, the points' share in a world of ranks, stay zero: it is inside the cameras' slots here)
+    // (kGradMaxPt and kXSqPt, the points' share in a world of ranks, stay zero: it is inside the cameras' slots here)
     ReduceRows rows;
     rows.n = 3;
-    rows.row[0] = 0; rows.count[0] = nb; rows.out[0] = b_scal_.p + 4;
-    rows.row[1] = 1; rows.count[1] = g; rows.is_max[1] = 1; rows.out[1] = b_scal_.p;
-    rows.row[2] = 2; rows.count[2] = g; rows.out[2] = b_scal_.p + 1;
+    rows.row[0] = 0; rows.count[0] = nb; rows.out[0] = b_scal_.p + kSumSq;
+    rows.row[1] = 1; rows.count[1] = g; rows.is_max[1] = 1; rows.out[1] = b_scal_.p + kGradMaxCam;
+    rows.row[2] = 2; rows.count[2] = g; rows.out[2] = b_scal_.p + kXSqCam;
     launch_final_reduce_rows(b_partial_.p, partial_stride_, rows, s);
   } else {
-  launch_final_reduce(b_partial_.p, partial_stride_, nb, 1, 0, b_scal_.p + 4, s);
+  launch_final_reduce(b_partial_.p, partial_stride_, nb, 1, 0, b_scal_.p + kSumSq, s);
   // cameras: every rank holds all of them — but in a segmented world only its own segment's (and the separator's) are
   // current, and the separator's |x|^2 must be counted once: the head's rank takes it
   int c_lo = 0, c_n = (int)nc;
@@ -1033,16 +1048,16 @@ int BalSolver::evaluate_with_jacobian(bool first) {
     const int lo2 = 9 * cam_b_, n2 = (int)nc - lo2;
     gc += launch_grad_max_xnorm(d_.gs_c + lo2, d_.scale_c + lo2, d_.xc + lo2, n2, b_partial_.p + gc, partial_stride_, s);
   }
-  launch_final_reduce(b_partial_.p, partial_stride_, gc, 2, 1, b_scal_.p, s);
+  launch_final_reduce(b_partial_.p, partial_stride_, gc, 2, 1, b_scal_.p + kGradMaxCam, s);
   // (the points this rank accounts for: all its own — not the copies of retained points whose home is another rank, which come last)
   const int np_own = 3 * P_own_;
   const int gp = launch_grad_max_xnorm(d_.gs_p, d_.scale_p, d_.xp, np_own, b_partial_.p + 2 * (size_t)partial_stride_, partial_stride_, s);
-  launch_final_reduce(b_partial_.p + 2 * (size_t)partial_stride_, partial_stride_, np_own ? gp : 0, 2, 1, b_scal_.p + 2, s);
+  launch_final_reduce(b_partial_.p + 2 * (size_t)partial_stride_, partial_stride_, np_own ? gp : 0, 2, 1, b_scal_.p + kGradMaxPt, s);
   }
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 5 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kEvalFirst, b_scal_.p + kEvalFirst, (kEvalLast + 1 - kEvalFirst) * sizeof(double), hipMemcpyDeviceToHost, s));
   if (bounded_) {  // max |x - P(x - g)|, |x|^2 and the active bounds in one launch (one device: the whole vector)
     kt_.begin("bounded_grad_max_xnorm", s); launch_bounded_grad_max_xnorm(b_gs_.p, b_scale_.p, d_.xc, (int)(nc + np), bd_, s); kt_.end("bounded_grad_max_xnorm", s);
-    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 40, bd_.scal + 3, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kBounds + kBdGradMax, bd_.scal + kBdGradMax, (kBdActive + 1 - kBdGradMax) * sizeof(double), hipMemcpyDeviceToHost, s));
   }
   }
   if (graph) {
@@ -1055,19 +1070,18 @@ int BalSolver::evaluate_with_jacobian(bool first) {
   const bool dev_gather = rank_table_on_device(3) && !graph;
   if (dev_gather) { int rc = enqueue_rank_table(0, 3); if (rc) return rc; }
   SK_HIP_TRY(hipStreamSynchronize(s));
-  const double sumsq = h_scal_[4];
-  const double gmax_c = h_scal_[0], x2_c = h_scal_[1];
+  const double sumsq = h_scal_[kSumSq];
+  const double gmax_c = h_scal_[kGradMaxCam], x2_c = h_scal_[kXSqCam];
   // local: sum r^2, max |g_p|, |x_p|^2 — and in a segmented world this rank's cameras' share of max |g_c| and |x_c|^2 too
-  double loc[3] = {sumsq, segmented_ ? std::max(h_scal_[2], gmax_c) : h_scal_[2], h_scal_[3] + (segmented_ ? x2_c : 0.0)};
+  double loc[3] = {sumsq, segmented_ ? std::max(h_scal_[kGradMaxPt], gmax_c) : h_scal_[kGradMaxPt], h_scal_[kXSqPt] + (segmented_ ? x2_c : 0.0)};
   const int ops3[3] = {0, 1, 0};
-  int rc = dev_gather ? fold_rank_table(loc, 3, ops3) : gather_rank_scalars(loc, 3, ops3);
+  int rc = dev_gather ? fold_rank_table(h_scal_ + kRankTable, loc, 3, ops3) : gather_rank_scalars(loc, 3, ops3);
   if (rc) return rc;
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvJac]) == hipSuccess) phase_[0] += 1e-3 * ms;
+  add_phases(0, 0);
   cost_ = 0.5 * loc[0];
   gmax_ = segmented_ ? loc[1] : std::max(gmax_c, loc[1]);
   xnorm_ = std::sqrt((segmented_ ? 0.0 : x2_c) + loc[2]);
-  if (bounded_) { gmax_ = h_scal_[40]; active_bounds_ = (long)h_scal_[42]; }
+  if (bounded_) { gmax_ = h_scal_[kBounds + kBdGradMax]; active_bounds_ = (long)h_scal_[kBounds + kBdActive]; }
   if (!std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
   return SK_OK;
 }
@@ -1075,56 +1089,110 @@ int BalSolver::evaluate_with_jacobian(bool first) {
 // A time-out of the resident panel chain (info == 2: the device is shared, or its kernels are being serialised) loses
 // that factorisation, not the step: the chain is switched off for the device and the same linear system is assembled
 // and factored again, launch by launch, in the same iteration — the trajectory does not change.
-int BalSolver::try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
-  if (dogleg()) return try_step_dogleg(radius, valid, mcc, new_cost, step_norm);
-  if (bounded_) return try_step_bounded(radius, valid, mcc, new_cost, step_norm);
+int BalSolver::linear_solve(double radius, LinearSolve* out) {
   bool chain_lost = false;
-  int rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
-  if (rc == SK_OK && chain_lost) rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
+  int rc = solve_once(radius, out, &chain_lost);
+  if (rc == SK_OK && chain_lost) rc = solve_once(radius, out, &chain_lost);
   return rc;
 }
 
-int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm, bool* chain_lost) {
+int BalSolver::solve_once(double radius, LinearSolve* out, bool* chain_lost) {
   hipStream_t s = stream_;
   *chain_lost = false;
-  const size_t nc = 9 * (size_t)C_;
-  *valid = false;
+  *out = LinearSolve();
   ++n_linear_solves_;
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   const bool graph = graph_ok();
   const bool replay = graph && g_step_[parity_] != nullptr;
   bool candidate_failed = false;  // a cost function that cannot be evaluated at the candidate: the step is rejected (cost = max)
   if (graph) {
-    h_scal_[32] = radius;  // pinned: the captured host-to-device copy reads it when the graph RUNS
-    if (!replay && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); graph_mode_ = false; return try_step_once(radius, valid, mcc, new_cost, step_norm, chain_lost); }
+    h_scal_[kRadius] = radius;  // pinned: the captured host-to-device copy reads it when the graph RUNS
+    if (!replay && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); graph_mode_ = false; return solve_once(radius, out, chain_lost); }
   }
   CaptureGuard capture(s, graph && !replay, &graph_mode_);
   if (!replay) {
-  // the LM diagonal is formed where it is used (bal_lm_diag): the radius travels in the kernel arguments, or — a replayed graph —
-  // through device memory
-  d_.lm_lo = opt_.min_lm_diagonal; d_.lm_hi = opt_.max_lm_diagonal; d_.lm_radius = radius; d_.lm_radius_dev = nullptr;
-  if (graph) {
-    SK_HIP_TRY(hipMemcpyAsync(b_scal_.p + 12, h_scal_ + 32, sizeof(double), hipMemcpyHostToDevice, s));
-    d_.lm_radius_dev = b_scal_.p + 12;
+    // the LM diagonal is formed where it is used (bal_lm_diag): the radius travels in the kernel arguments, or — a replayed graph —
+    // through device memory
+    d_.lm_lo = opt_.min_lm_diagonal; d_.lm_hi = opt_.max_lm_diagonal; d_.lm_radius = radius; d_.lm_radius_dev = nullptr;
+    if (graph) {
+      SK_HIP_TRY(hipMemcpyAsync(b_scal_.p + kRadiusDev, h_scal_ + kRadius, sizeof(double), hipMemcpyHostToDevice, s));
+      d_.lm_radius_dev = b_scal_.p + kRadiusDev;
+    }
+    // (this step's back-substitution zeroes what it reads when it is the resident launch: decided here, once, for the whole step)
+    // (... and whether the back-substitutions of this step are the resident launch at all: one decision for every front — the process-wide
+    // switch can be cleared by another solver's time-out at any moment)
+    Backsolve bs;
+    bs.resident = opt_.resident_kernels && cholesky_backsolve_resident(npad_ / 128) ? 1 : 0;
+    bs.zero_after = zero_by_backsolve_ && bs.resident;
+    int rc = enqueue_schur_assembly(bs, graph);
+    if (rc == SK_OK) rc = enqueue_factor_backsolve(bs, graph);
+    if (rc == SK_OK) rc = enqueue_point_backsub(graph);
+    if (rc == SK_OK && !dogleg()) rc = enqueue_candidate_cost(2, &candidate_failed);  // (DOGLEG: the candidate is formed and evaluated by dogleg_trial)
+    if (rc) return rc;
+    if (!graph) SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kStepFirst, b_scal_.p + kStepFirst, (kStepLast + 1 - kStepFirst) * sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  // ---- B. Schur complement assembly ----
-  // (this step's back-substitution zeroes what it reads when it is the resident launch: decided here, once, for the whole step)
-  // (... and whether the back-substitutions of this step are the resident launch at all: one decision for every front — the process-wide
-  // switch can be cleared by another solver's time-out at any moment)
-  const int bs_resident = opt_.resident_kernels && cholesky_backsolve_resident(npad_ / 128) ? 1 : 0;
-  const bool zero_after = zero_by_backsolve_ && bs_resident;
+  const bool dev_gather = rank_table_on_device(4) && !graph;  // (see evaluate_with_jacobian)
+  if (dev_gather) { int rc = enqueue_rank_table(1, 4); if (rc) return rc; }
+  if (graph) {
+    if (!replay) { capture.release(); int rc = finish_capture(s, &g_step_[parity_]); if (rc) return rc; if (!graph_mode_) return solve_once(radius, out, chain_lost); }
+    SK_HIP_TRY(hipGraphLaunch(g_step_[parity_], s));
+    SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
+  }
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  if (graph) {  // one replayed graph: no events inside it — the whole linear solve + candidate evaluation is reported as "factor"
+    add_phase(2, ev_[kEvBegin], ev_[kEvCost]);
+  } else {
+    add_phases(1, 4);
+  }
+  const int fail = host_flag(kFail), info = host_flag(kInfo);
+  if (info != 0) need_full_zero_ = true;  // (a pivot that was not positive, a wait that gave up: whatever the back-substitution did, start from a clean envelope)
+  if (cholesky_note_info(opt_.lookahead ? &chol_ctx_ : nullptr, info) && !opt_.allreduce) {  // factor again, launch by launch
+    if (graph_mode_) {
+      // a replayed graph would launch the resident kernel that has just timed out again and again (the choice is made at capture): the
+      // iteration is enqueued launch by launch from here on
+      for (hipGraphExec_t* g : {&g_step_[0], &g_step_[1], &g_eval_[0], &g_eval_[1]}) if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
+      graph_mode_ = false;
+    }
+    *chain_lost = true;
+    return SK_OK;
+  }
+  if (dogleg()) {  // (one device.  Not valid: a pivot or a point block's 3 x 3 was not positive — the damped system is not positive definite at this mu)
+    out->valid = (fail | info) == 0;
+    out->dl = dogleg::Scalars::from(h_scal_ + kDogleg + kDlScalars);
+    return SK_OK;
+  }
+  // sum r_new^2, model term, |delta_p|^2 (segmented: + this rank's cameras' |delta_c|^2, which no other rank has), failure
+  double loc[4] = {h_scal_[kCandSumSq], h_scal_[kModel], h_scal_[kStepSqPt] + (segmented_ ? h_scal_[kStepSqCam] : 0.0), (double)(fail | info)};
+  const int ops4[4] = {0, 0, 0, 1};
+  int rc = dev_gather ? fold_rank_table(h_scal_ + kRankTable, loc, 4, ops4) : gather_rank_scalars(loc, 4, ops4);
+  if (rc) return rc;
+  if (opt_.allreduce && loc[3] >= 2.0) cholesky_disable_chain(&chol_ctx_);  // a rank's chain timed out (info == 2): launch by launch on every rank from here on
+  const double step_sq = (segmented_ ? 0.0 : h_scal_[kStepSqCam]) + loc[2];
+  if (loc[3] != 0.0 || !std::isfinite(step_sq) || !std::isfinite(loc[1])) return SK_OK;  // invalid step
+  out->valid = true;
+  out->model_cost_change = -loc[1];
+  out->cost = candidate_failed ? std::numeric_limits<double>::max() : 0.5 * loc[0];
+  out->step_norm = std::sqrt(bounded_ ? h_scal_[kBounds + kBdStepSq] : step_sq);
+  out->g_delta = h_scal_[kBounds + kBdGDelta]; out->max_delta = h_scal_[kBounds + kBdMaxDelta];  // (of this solve under bounds only, where they are read)
+  return SK_OK;
+}
+
+// ---- B. Schur complement assembly ----
+int BalSolver::enqueue_schur_assembly(const Backsolve& bs, bool graph) {
+  hipStream_t s = stream_;
   kt_.begin("memset_S", s);
   for (int f = 0; f < 3; ++f)
     if (fr_[f].nblk > 0) launch_zero_envelope(d_.front[f].S, (int)fr_[f].dim, (zero_by_backsolve_ && !need_full_zero_) ? b_zero_min_f_[f].p : b_zero_col0_f_[f].p, fr_[f].nblk, s);
   kt_.end("memset_S", s);
-  need_full_zero_ = !zero_after;
-  SK_HIP_TRY(hipMemsetAsync(b_scal_.p + 14, 0, 2 * sizeof(double), s));  // the failure flag and the factorisation's info
+  need_full_zero_ = !bs.zero_after;
+  SK_HIP_TRY(hipMemsetAsync(b_scal_.p + kFail, 0, (kInfo + 1 - kFail) * sizeof(double), s));  // the failure flag and the factorisation's info
   launch_bal_point_block(d_, s);
   launch_bal_kept_points(d_, s);  // (retained points: their rows of the reduced system; nothing of theirs enters the Schur complement)
   launch_bal_obs_precompute(d_, s);
   kt_.begin("bal_cam_diag", s); launch_bal_cam_diag(d_, s); kt_.end("bal_cam_diag", s);
   kt_.begin("bal_pair", s); launch_bal_pair(d_, s); kt_.end("bal_pair", s);
-  if (opt_.allreduce && !segmented_) {  // (segmented: the root front is summed after the leaf has been factored, below)
+  if (opt_.allreduce && !segmented_) {  // (segmented: the root front is summed after the leaf has been factored)
     // sum S (with the rhs row) over ranks: only its lower block triangle travels (half the bytes)
     launch_tri_pack(d_.S, npad_, b_pack_.p, npad_ / 128, b_pack_col0_.p, b_pack_off_.p, true, s);  // (never dissected here: front[2] is the whole system)
     int rc = allreduce(b_pack_.p, packed_elems_);
@@ -1134,11 +1202,6 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
   // D_c^2 onto the cameras' diagonal entries; the padded tails of the interiors and of the root are identities, and the
   // augmented right-hand-side row of the root gets a huge diagonal so that its factorisation stays positive definite (the
   // entry itself is unused; in a leaf's border that diagonal stays zero: it is ADDED to the root's)
-  auto finish_root = [&]() {
-    launch_bal_finish_S(d_, 4, s);
-    launch_set_diagonal(d_.front[2].S, (int)fr_[2].dim, fr_[2].rhs_row, fr_[2].rhs_row + 1, 1e300, s);
-    launch_set_diagonal(d_.front[2].S, (int)fr_[2].dim, fr_[2].rhs_row + 1, (int)fr_[2].dim, 1.0, s);
-  };
   if (!segmented_) {
     // one launch: D^2 of every camera, the identities on the leaf fronts' padding, the root's two diagonal ranges
     BalFinishRanges r;
@@ -1152,17 +1215,22 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
     launch_bal_finish_S(d_, 3, s);
     for (int f = 0; f < 2; ++f)
       if (fr_[f].nblk > 0) launch_set_diagonal(d_.front[f].S, (int)fr_[f].dim, 9 * fr_[f].cams, fr_[f].ncols * 128, 1.0, s);
-    // (segmented: finish_root() after the ranks' root fronts have been summed — D^2 and the diagonals are added once)
+    // (the root's D^2 and diagonals: after the ranks' root fronts have been summed — they are added once)
   }
   if (!graph) SK_HIP_TRY(hipEventRecord(ev_[kEvAssemble], s));
-  // ---- C. dense Cholesky + solves ----
+  return SK_OK;
+}
+
+// ---- C. dense Cholesky + solves: segmented over ranks, dissected on one device, or a single front ----
+int BalSolver::enqueue_factor_backsolve(const Backsolve& bs, bool graph) {
+  hipStream_t s = stream_;
   CholeskyContext* ctx = opt_.lookahead ? &chol_ctx_ : nullptr;
-  int* bs_info = bs_resident ? info_p_ : nullptr;  // (nullptr: the back-substitutions one launch per block step — nothing resident, nothing that waits)
+  int* bs_info = bs.resident ? info_p_ : nullptr;  // (nullptr: the back-substitutions one launch per block step — nothing resident, nothing that waits)
   double* yf[3] = {b_yf_.p + fr_[0].y_off, b_yf_.p + fr_[1].y_off, b_yf_.p + fr_[2].y_off};
   double* wf[3] = {b_wf_.p + fr_[0].y_off, b_wf_.p + fr_[1].y_off, b_wf_.p + fr_[2].y_off};
   // (the resident back-substitutions find their "not there yet" pattern in every front's y already: one fill here, in front of the
   // factorisation, instead of one in front of each of them, between the factorisation's end and the first hop)
-  const bool prefilled = bs_resident != 0;
+  const bool prefilled = bs.resident != 0;
   if (prefilled) SK_HIP_TRY(hipMemsetAsync(b_yf_.p, 0xff, (fr_[0].dim + fr_[1].dim + fr_[2].dim) * sizeof(double), s));
   if (segmented_) {
     // this rank's segment: factor its interior, leave its Schur complement on the separators next to it; sum the root
@@ -1181,187 +1249,101 @@ int BalSolver::try_step_once(double radius, bool* valid, double* mcc, double* ne
     int rc = allreduce(b_pack_.p, packed_elems_);
     if (rc) return rc;
     launch_tri_pack(Rs, (int)R.dim, b_pack_.p, R.nblk, b_pack_col0_.p, b_pack_off_.p, false, s);
-    finish_root();
+    // the root's D^2, its right-hand-side row's huge diagonal, the identity on its padding: once, on the sum
+    launch_bal_finish_S(d_, 4, s);
+    launch_set_diagonal(Rs, (int)R.dim, R.rhs_row, R.rhs_row + 1, 1e300, s);
+    launch_set_diagonal(Rs, (int)R.dim, R.rhs_row + 1, (int)R.dim, 1.0, s);
     cholesky_factor(Rs, (long)R.dim, (int)R.dim, RLinv, info_p_, group_, s, ctx, &kt_, R.env(), chain_ok(), -1, 1, nullptr, R.tl());
-    cholesky_backsolve(Rs, (long)R.dim, 9 * R.cams, (int)R.dim, R.rhs_row, RLinv, wf[2], yf[2], s, &kt_, R.env(), bs_info, R.tl(), zero_after, bs_resident, prefilled);
+    cholesky_backsolve(Rs, (long)R.dim, 9 * R.cams, (int)R.dim, R.rhs_row, RLinv, wf[2], yf[2], s, &kt_, R.env(), bs_info, R.tl(), bs.zero_after, bs.resident, prefilled);
     if (L.ncols > 0) {
       cholesky_gather_map(yf[2], b_leaf_gmap_.p, b_ybB_.p, (L.nblk - L.ncols) * 128, s);
-      cholesky_backsolve_front(L.S, L.ld, L.nblk, L.ncols, L.rhs_row, L.Linv, b_ybB_.p, wf[0], yf[0], s, L.last, L.spike, L.tail_rows, bs_info, zero_after, L.tail, nullptr, bs_resident, prefilled);
+      cholesky_backsolve_front(L.S, L.ld, L.nblk, L.ncols, L.rhs_row, L.Linv, b_ybB_.p, wf[0], yf[0], s, L.last, L.spike, L.tail_rows, bs_info, bs.zero_after, L.tail, nullptr, bs.resident, prefilled);
     }
   } else if (dissected_) {
     cholesky_dissected_factor(ds_, info_p_, group_, s, ctx, &chol_ctx_b_, &kt_, &kt_b_, chain_ok());
-    cholesky_dissected_backsolve(ds_, 9 * fr_[2].cams, wf[2], yf[2], wf[0], yf[0], wf[1], yf[1], b_ybB_.p, s, &chol_ctx_b_, &kt_, bs_info, zero_after, bs_resident, prefilled);
+    cholesky_dissected_backsolve(ds_, 9 * fr_[2].cams, wf[2], yf[2], wf[0], yf[0], wf[1], yf[1], b_ybB_.p, s, &chol_ctx_b_, &kt_, bs_info, bs.zero_after, bs.resident, prefilled);
   } else {
     const FrontHost& R = fr_[2];
     cholesky_factor(d_.front[2].S, (long)R.dim, (int)R.dim, b_Linv_.p, info_p_, group_, s, ctx, &kt_, R.env(), chain_ok(), -1, 1, nullptr, R.tl());
-    cholesky_backsolve(d_.front[2].S, (long)R.dim, n_, (int)R.dim, R.rhs_row, b_Linv_.p, wf[2], yf[2], s, &kt_, R.env(), bs_info, R.tl(), zero_after, bs_resident, prefilled);
+    cholesky_backsolve(d_.front[2].S, (long)R.dim, n_, (int)R.dim, R.rhs_row, b_Linv_.p, wf[2], yf[2], s, &kt_, R.env(), bs_info, R.tl(), bs.zero_after, bs.resident, prefilled);
   }
   if (!graph) SK_HIP_TRY(hipEventRecord(ev_[kEvChol], s));
-  // ---- D. back-substitution, candidate point ----
-  {
-    // whose cameras' steps this rank accounts for in |step|^2: all, or (segmented) its segment's, + the separator's on the head's rank
-    int lo = 0, hi = (int)nc, lo2 = 0, hi2 = 0;
-    if (segmented_) {
-      lo = 9 * my_lo_; hi = 9 * my_hi_;
-      if (role_ == 0) { lo2 = 9 * cam_b_; hi2 = (int)nc; }
-    }
-    launch_bal_backsub(d_, b_scal_.p + 8, lo, hi, lo2, hi2, s);  // (|delta_c|^2 to slot 8, |delta_p|^2 to slot 9)
+  return SK_OK;
+}
+
+// ---- D. back-substitution of the points, and the strategy's vectors behind it (counted with the back-substitution) ----
+int BalSolver::enqueue_point_backsub(bool graph) {
+  hipStream_t s = stream_;
+  // whose cameras' steps this rank accounts for in |step|^2: all, or (segmented) its segment's, + the separator's on the head's rank
+  int lo = 0, hi = 9 * C_, lo2 = 0, hi2 = 0;
+  if (segmented_) {
+    lo = 9 * my_lo_; hi = 9 * my_hi_;
+    if (role_ == 0) { lo2 = 9 * cam_b_; hi2 = 9 * C_; }
   }
-  if (dogleg()) {  // the two vectors of this Jacobian and their eight scalars (counted with the back-substitution)
+  launch_bal_backsub(d_, b_scal_.p + kStepSqCam, lo, hi, lo2, hi2, s);  // (and |delta_p|^2 to kStepSqPt)
+  if (dogleg()) {  // the two vectors of this Jacobian and their eight scalars
     kt_.begin("dogleg_vector_norms", s); launch_dogleg_vector_norms(d_, dl_, s); kt_.end("dogleg_vector_norms", s);
     kt_.begin("bal_dogleg_products", s); launch_bal_dogleg_products(d_, dl_, s); kt_.end("bal_dogleg_products", s);
     launch_dogleg_reduce_scalars(dl_, s);
-    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, dl_.scal, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kDogleg + kDlScalars, dl_.scal + kDlScalars, (kDlStepSq - kDlScalars) * sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  if (bounded_) {  // g . delta and max |delta_j| of the unconstrained step; the candidate becomes P(x + delta) (counted with the back-substitution)
+  if (bounded_) {  // g . delta and max |delta_j| of the unconstrained step; the candidate becomes P(x + delta)
     kt_.begin("bal_directional_derivative", s); launch_bal_directional_derivative(d_, bd_, s); kt_.end("bal_directional_derivative", s);
     kt_.begin("bal_bounded_candidate", s); launch_bal_bounded_candidate(d_, bd_, 1.0, s); kt_.end("bal_bounded_candidate", s);
-    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 44, bd_.scal, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kBounds + kBdStepSq, bd_.scal + kBdStepSq, (kBdMaxDelta + 1 - kBdStepSq) * sizeof(double), hipMemcpyDeviceToHost, s));
   }
   if (!graph) SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
-  if (!dogleg()) {  // (DOGLEG: the candidate is formed and evaluated by dogleg_candidate)
+  return SK_OK;
+}
+
+// The cost of the point in xc_new / xp_new: the cost kernel (or the tape's), the host-evaluated blocks, the reduction of `rows` rows of
+// partial sums to kCandSumSq (and kModel).
+int BalSolver::enqueue_candidate_cost(int rows, bool* failed) {
+  hipStream_t s = stream_;
   kt_.begin("bal_eval_cost", s);
   if (tape_mode_) launch_bal_eval_cost_tape(d_, tape_dev_, s); else launch_bal_eval_cost(d_, s);
   kt_.end("bal_eval_cost", s);
   int nb_cost = bal_partial_blocks(N_);
   if (d_.num_host > 0) {
-    int rc = host_callbacks(d_.xc_new, false, &candidate_failed);
+    int rc = host_callbacks(d_.xc_new, false, failed);
     if (rc) return rc;
     nb_cost += launch_bal_host_cost(d_, nb_cost, s);
   }
-  launch_final_reduce(b_partial_.p, partial_stride_, nb_cost, 2, 0, b_scal_.p, s);
-  }
-  if (!graph) SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 16 * sizeof(double), hipMemcpyDeviceToHost, s));  // scalars 0-9, the two flags in 14 and 15
-  }
-  const bool dev_gather = rank_table_on_device(4) && !graph;  // (see evaluate_with_jacobian)
-  if (dev_gather) { int rc = enqueue_rank_table(1, 4); if (rc) return rc; }
-  if (graph) {
-    if (!replay) { capture.release(); int rc = finish_capture(s, &g_step_[parity_]); if (rc) return rc; if (!graph_mode_) return try_step_once(radius, valid, mcc, new_cost, step_norm, chain_lost); }
-    SK_HIP_TRY(hipGraphLaunch(g_step_[parity_], s));
-    SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
-  }
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (graph) {  // one replayed graph: no events inside it — the whole linear solve + candidate evaluation is reported as "factor"
-    if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvCost]) == hipSuccess) phase_[2] += 1e-3 * ms;
-  } else {
-    if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvAssemble]) == hipSuccess) phase_[1] += 1e-3 * ms;
-    if (hipEventElapsedTime(&ms, ev_[kEvAssemble], ev_[kEvChol]) == hipSuccess) phase_[2] += 1e-3 * ms;
-    if (hipEventElapsedTime(&ms, ev_[kEvChol], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
-    if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
-  }
-  int fail = 0, info = 0;
-  std::memcpy(&fail, h_scal_ + 14, sizeof(int)); std::memcpy(&info, h_scal_ + 15, sizeof(int));
-  if (info != 0) need_full_zero_ = true;  // (a pivot that was not positive, a wait that gave up: whatever the back-substitution did, start from a clean envelope)
-  if (cholesky_note_info(opt_.lookahead ? &chol_ctx_ : nullptr, info) && !opt_.allreduce) {  // factor again, launch by launch
-    if (graph_mode_) {
-      // a replayed graph would launch the resident kernel that has just timed out again and again (the choice is made at capture): the
-      // iteration is enqueued launch by launch from here on
-      for (hipGraphExec_t* g : {&g_step_[0], &g_step_[1], &g_eval_[0], &g_eval_[1]}) if (*g) { (void)hipGraphExecDestroy(*g); *g = nullptr; }
-      graph_mode_ = false;
-    }
-    *chain_lost = true;
-    return SK_OK;
-  }
-  if (dogleg()) { *valid = (fail | info) == 0; return SK_OK; }  // (one device; the scalars are in h_scal_[16..23])
-  // sum r_new^2, model term, |delta_p|^2 (segmented: + this rank's cameras' |delta_c|^2, which no other rank has), failure
-  double loc[4] = {h_scal_[0], h_scal_[1], h_scal_[9] + (segmented_ ? h_scal_[8] : 0.0), (double)(fail | info)};
-  const int ops4[4] = {0, 0, 0, 1};
-  int rc = dev_gather ? fold_rank_table(loc, 4, ops4) : gather_rank_scalars(loc, 4, ops4);
-  if (rc) return rc;
-  if (opt_.allreduce && loc[3] >= 2.0) cholesky_disable_chain(&chol_ctx_);  // a rank's chain timed out (info == 2): launch by launch on every rank from here on
-  const double step_sq = (segmented_ ? 0.0 : h_scal_[8]) + loc[2];
-  if (loc[3] != 0.0 || !std::isfinite(step_sq) || !std::isfinite(loc[1])) return SK_OK;  // invalid step
-  *valid = true;
-  *mcc = -loc[1];
-  *new_cost = candidate_failed ? std::numeric_limits<double>::max() : 0.5 * loc[0];
-  *step_norm = std::sqrt(bounded_ ? h_scal_[44] : step_sq);
+  launch_final_reduce(b_partial_.p, partial_stride_, nb_cost, rows, 0, b_scal_.p + kCandSumSq, s);
   return SK_OK;
 }
 
-// Parameter bounds (common.hpp: namespace bounds).  The linear solve and the model's cost change are the unconstrained
-// step's at this radius; the candidate is P(x + alpha delta), alpha from the line search.  phi(1) came with the solve.
-int BalSolver::try_step_bounded(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
-  bool chain_lost = false;
-  int rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
-  if (rc == SK_OK && chain_lost) rc = try_step_once(radius, valid, mcc, new_cost, step_norm, &chain_lost);
-  if (rc || !*valid) return rc;
-  return line_search(h_scal_[45], h_scal_[46], new_cost, step_norm);
-}
-
-int BalSolver::bounded_trial(double alpha, double* cost, double* step_norm) {
+// What the two trials share behind the launch that formed their candidate (since kEvBegin): its cost — the model term of the cost kernel
+// is not used here — the copies of the sum and of the candidate's |x - x_new|^2 (a device scalar of the strategy, to its pinned mirror),
+// the one synchronisation, phases 3 and 4.  One device, no host-evaluated blocks (setup(), refuses_bounds()).
+int BalSolver::trial_cost(const double* step_sq_dev, int step_sq_slot, double* cost, double* step_norm) {
   hipStream_t s = stream_;
-  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
-  kt_.begin("bal_bounded_candidate", s); launch_bal_bounded_candidate(d_, bd_, alpha, s); kt_.end("bal_bounded_candidate", s);
   SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
-  kt_.begin("bal_eval_cost", s);
-  if (tape_mode_) launch_bal_eval_cost_tape(d_, tape_dev_, s); else launch_bal_eval_cost(d_, s);  // (its model term: not used here)
-  kt_.end("bal_eval_cost", s);
-  launch_final_reduce(b_partial_.p, partial_stride_, bal_partial_blocks(N_), 1, 0, b_scal_.p, s);
-  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, sizeof(double), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 44, bd_.scal, sizeof(double), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
-  *cost = 0.5 * h_scal_[0];
-  *step_norm = std::sqrt(h_scal_[44]);
-  return SK_OK;
-}
-
-// DOGLEG (common.hpp: namespace dogleg).  A new Jacobian: the Gauss-Newton solve at the current mu, again at ten times
-// mu while the factorisation finds the system not positive definite; then, and after every rejected step, the candidate of the
-// radius from the two vectors on the device.
-int BalSolver::try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
-  *valid = false;
-  d_.lm_lo = opt_.min_lm_diagonal; d_.lm_hi = opt_.max_lm_diagonal;
-  if (!dl_reuse_) {
-    bool solved = false;
-    while (dl_mu_ < dogleg::kMaxMu) {
-      bool chain_lost = false, ok = false;
-      int rc = try_step_once(1.0 / dl_mu_, &ok, mcc, new_cost, step_norm, &chain_lost);
-      if (rc == SK_OK && chain_lost) rc = try_step_once(1.0 / dl_mu_, &ok, mcc, new_cost, step_norm, &chain_lost);
-      if (rc) return rc;
-      if (ok && !chain_lost) { solved = true; break; }
-      // not ok: the factorisation met a pivot that is not positive, or a point block's 3 x 3 did (the fail flag); both mean the
-      // damped system is not positive definite at this mu, and each further solve counts in "linear_solves"
-      dl_mu_ *= dogleg::kMuIncreaseFactor;
-    }
-    if (!solved) return SK_OK;  // invalid step
-    dl_k_ = dogleg::Scalars::from(h_scal_ + 16);
-  } else {
-    ++n_dl_reused_;
-  }
-  if (!dogleg::interpolate(dl_k_, radius, &dl_a_, &dl_b_, &dl_step_norm_, mcc)) return SK_OK;
   bool failed = false;
-  int rc = dogleg_candidate(dl_a_, dl_b_, new_cost, step_norm, &failed);
+  int rc = enqueue_candidate_cost(1, &failed);
   if (rc) return rc;
-  *valid = !failed;
+  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kCandSumSq, b_scal_.p + kCandSumSq, sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + step_sq_slot, step_sq_dev, sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  add_phases(3, 4);
+  *cost = failed ? std::numeric_limits<double>::max() : 0.5 * h_scal_[kCandSumSq];  // (as the LM path; no host-evaluated block reaches a trial today)
+  *step_norm = std::sqrt(h_scal_[step_sq_slot]);
   return SK_OK;
 }
 
-int BalSolver::dogleg_candidate(double a, double b, double* new_cost, double* step_norm, bool* failed) {
-  hipStream_t s = stream_;
-  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
-  kt_.begin("bal_dogleg_combine", s); launch_bal_dogleg_combine(d_, dl_, a, b, s); kt_.end("bal_dogleg_combine", s);
-  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
-  kt_.begin("bal_eval_cost", s);
-  if (tape_mode_) launch_bal_eval_cost_tape(d_, tape_dev_, s); else launch_bal_eval_cost(d_, s);  // (its model term: not used here)
-  kt_.end("bal_eval_cost", s);
-  launch_final_reduce(b_partial_.p, partial_stride_, bal_partial_blocks(N_), 1, 0, b_scal_.p, s);
-  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, sizeof(double), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 24, dl_.scal + 8, sizeof(double), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
-  *failed = !std::isfinite(h_scal_[24]);
-  *new_cost = 0.5 * h_scal_[0];
-  *step_norm = std::sqrt(h_scal_[24]);
-  return SK_OK;
+// Parameter bounds (common.hpp: namespace bounds): the candidate P(x + alpha delta) of the line search.
+int BalSolver::bounded_trial(double alpha, double* cost, double* step_norm) {
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], stream_));
+  kt_.begin("bal_bounded_candidate", stream_); launch_bal_bounded_candidate(d_, bd_, alpha, stream_); kt_.end("bal_bounded_candidate", stream_);
+  return trial_cost(bd_.scal + kBdStepSq, kBounds + kBdStepSq, cost, step_norm);
+}
+
+// DOGLEG (common.hpp: namespace dogleg): the candidate x + (a s + b g) scale from the two vectors on the device.
+int BalSolver::dogleg_trial(double a, double b, double* cost, double* step_norm) {
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], stream_));
+  kt_.begin("bal_dogleg_combine", stream_); launch_bal_dogleg_combine(d_, dl_, a, b, stream_); kt_.end("bal_dogleg_combine", stream_);
+  return trial_cost(dl_.scal + kDlStepSq, kDogleg + kDlStepSq, cost, step_norm);
 }
 
 // End the capture on `s` and instantiate what was captured.  A runtime that cannot capture this sequence switches the

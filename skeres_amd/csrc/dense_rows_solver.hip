@@ -41,7 +41,7 @@ class DenseRowsSolver : public SolverBase {
  protected:
   int setup() override;
   int evaluate_with_jacobian(bool first) override;
-  int try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) override;
+  int linear_solve(double radius, LinearSolve* out) override;  // Levenberg-Marquardt only: DOGLEG and bounds are refused (SolverBase)
   void accept_candidate() override { std::swap(x_, x_new_); }
   int write_back() override;
   void describe(Summary* s) override {
@@ -159,16 +159,15 @@ int DenseRowsSolver::evaluate_with_jacobian(bool first) {
   SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   SK_HIP_TRY(hipEventRecord(ev_[kEvJac], s));
   SK_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvJac]) == hipSuccess) phase_[0] += 1e-3 * ms;
+  add_phases(0, 0);
   cost_ = 0.5 * h_scal_[0]; gmax_ = h_scal_[1]; xnorm_ = std::sqrt(h_scal_[2]);
   if (!std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
   return SK_OK;
 }
 
-int DenseRowsSolver::try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
+int DenseRowsSolver::linear_solve(double radius, LinearSolve* out) {
   hipStream_t s = stream_;
-  *valid = false;
+  *out = LinearSolve();
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   launch_lm_diagonal(b_colsq_.p, b_D_.p, n_, opt_.min_lm_diagonal, opt_.max_lm_diagonal, radius, s);
   SK_HIP_TRY(hipMemsetAsync(b_info_.p, 0, sizeof(int), s));
@@ -198,17 +197,13 @@ int DenseRowsSolver::try_step(double radius, bool* valid, double* mcc, double* n
   SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
   SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, b_info_.p, sizeof(int), hipMemcpyDeviceToHost, s));
   SK_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvAssemble]) == hipSuccess) phase_[1] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvAssemble], ev_[kEvChol]) == hipSuccess) phase_[2] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvChol], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
+  add_phases(1, 4);
   int info = 0; std::memcpy(&info, h_scal_ + 16, sizeof(int));
   if (info || !std::isfinite(h_scal_[0]) || !std::isfinite(h_scal_[1])) return SK_OK;  // invalid step
-  *valid = true;
-  *step_norm = std::sqrt(h_scal_[0]);
-  *mcc = -h_scal_[1];
-  *new_cost = std::isfinite(h_scal_[2]) ? 0.5 * h_scal_[2] : std::numeric_limits<double>::infinity();
+  out->valid = true;
+  out->step_norm = std::sqrt(h_scal_[0]);
+  out->model_cost_change = -h_scal_[1];
+  out->cost = std::isfinite(h_scal_[2]) ? 0.5 * h_scal_[2] : std::numeric_limits<double>::infinity();
   return SK_OK;
 }
 

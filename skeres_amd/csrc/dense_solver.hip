@@ -25,16 +25,14 @@ class DenseSolver : public SolverBase {
  protected:
   int setup() override;
   int evaluate_with_jacobian(bool first) override;
-  int try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) override;
-  // DOGLEG over residual blocks without tangent-space blocks (setup() refuses those): the linear solve at radius 1 / mu, then, and
-  // after every rejected step, the candidate of the radius from s and g
-  int try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm);
-  int enqueue_linear_solve(double radius);  // D from the radius, the normal equations or the QR, y; records kEvAssemble and kEvChol
-  bool supports_dogleg() const override { return true; }
-  // Parameter bounds: try_step forms P(x + delta) (tangent_: the clamp follows Plus) and runs the line search; every further trial is
-  // bounded_trial (the candidate launch, the cost evaluation)
-  const char* refuses_bounds() const override { return nullptr; }
+  // SolverBase's three stepping virtuals.  DOGLEG is over residual blocks without tangent-space blocks (setup() refuses those)
+  int linear_solve(double radius, LinearSolve* out) override;
+  int dogleg_trial(double a, double b, double* cost, double* step_norm) override;
   int bounded_trial(double alpha, double* cost, double* step_norm) override;
+  int enqueue_linear_solve(double radius);  // D from the radius, the normal equations or the QR, y; records kEvAssemble and kEvChol
+  int candidate_cost(bool after_solve, double* cost, double* step_norm);
+  bool supports_dogleg() const override { return true; }
+  const char* refuses_bounds() const override { return nullptr; }  // (tangent_: the clamp follows Plus)
   void accept_candidate() override { std::swap(x_, x_new_); }
   int write_back() override;
   void describe(Summary* s) override {
@@ -64,8 +62,23 @@ class DenseSolver : public SolverBase {
   }
 
  private:
-  DevBuf<double> b_dl_vec_, b_dl_scal_;  // DOGLEG: [s | g]; the eight scalars and |x - x_new|^2
-  DevBuf<double> b_bd_box_, b_bd_scal_;  // bounds: [lo | hi] over x; |x - x_new|^2, g . delta, max |delta_j|, then the gradient test's three
+  // The scalars that cross PCIe.  b_scal_ (device) holds one block that every evaluation and every candidate copies back to the same
+  // slots of h_scal_ (pinned) in one copy; behind the block h_scal_ holds the flags and the mirrors of the strategies' own buffers.
+  enum Slot {
+    kSumSq = 0, kGradMax, kXSq,             // after evaluate_with_jacobian: sum r^2 (or of the loss terms), max |g|, |x|^2
+    kStepSq = 0, kModel, kCandSumSq,        // after a candidate: |x - x_new|^2 (every kernel that forms one), the model term, the candidate's sum r^2
+    kBlockFirst = 0, kBlockLast = kCandSumSq,
+    kDevSlots = 16,                         // b_scal_'s allocation
+    kFail = kBlockLast + 1, kInfo, kOk,     // h_scal_ only from here.  Three int flags, one double slot each (host_flag): b_fail_, b_info_, b_ok_
+    kDogleg,                                // the eight dogleg::Scalars (b_dl_scal_ + kDlScalars)
+    kBounds = kDogleg + kDlStepSq,          // mirror of b_bd_scal_ (BoundsScal)
+    kHostSlots = kBounds + kBdScalCount
+  };
+  static_assert(kXSq == kBlockLast && kBlockLast < kDevSlots, "one block, inside b_scal_");
+  static_assert(kBlockLast < kFail && kOk < kDogleg && kDogleg + (kDlStepSq - kDlScalars) <= kBounds, "h_scal_'s regions do not overlap");
+  int host_flag(int slot) const { int v = 0; std::memcpy(&v, h_scal_ + slot, sizeof(int)); return v; }
+  DevBuf<double> b_dl_vec_, b_dl_scal_;  // DOGLEG: [s | g]; the eight scalars
+  DevBuf<double> b_bd_box_, b_bd_scal_;  // bounds: [lo | hi] over x; BoundsScal (its kBdStepSq is not used here: b_scal_'s is)
   DevBuf<int> b_bd_ambient_;             // tangent coordinate -> coordinate of x (dense_kernels.hpp)
   int evaluate(const double* x_dev, bool jac);
   int host_callbacks(const double* x_dev, bool jac);
@@ -182,9 +195,9 @@ int DenseSolver::setup() {
   } else {
     SK_HIP_TRY(b_A_.alloc((size_t)(m_ + n_) * n_)); SK_HIP_TRY(b_b_.alloc(m_ + n_));
   }
-  SK_HIP_TRY(b_y_.alloc(npad_)); SK_HIP_TRY(b_w_.alloc(npad_)); SK_HIP_TRY(b_scal_.alloc(16));
+  SK_HIP_TRY(b_y_.alloc(npad_)); SK_HIP_TRY(b_w_.alloc(npad_)); SK_HIP_TRY(b_scal_.alloc(kDevSlots));
   SK_HIP_TRY(b_fail_.alloc(1)); SK_HIP_TRY(b_fail_.zero(s)); SK_HIP_TRY(b_info_.alloc(1)); SK_HIP_TRY(b_info_.zero(s)); SK_HIP_TRY(b_ok_.alloc(1));
-  SK_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_scal_), 64 * sizeof(double), hipHostMallocDefault));
+  SK_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_scal_), kHostSlots * sizeof(double), hipHostMallocDefault));
   if (dogleg()) { SK_HIP_TRY(b_dl_vec_.alloc(2 * (size_t)n_)); SK_HIP_TRY(b_dl_scal_.alloc(16)); SK_HIP_TRY(b_dl_scal_.zero(s)); }
   if (bounded_) {  // the box in the layout of x, and x projected onto it before the first evaluation
     std::vector<double> box(2 * (size_t)ng_);
@@ -283,23 +296,21 @@ int DenseSolver::evaluate_with_jacobian(bool first) {
     launch_dense_scale(b_J_.p, b_scale_.p, m_, n_, s);
     launch_apply_scale_to_reductions(b_colsq_.p, b_gs_.p, b_scale_.p, n_, s);
   }
-  if (has_loss_) launch_dense_sum(b_cterm_.p, m_, b_scal_.p, s); else launch_dense_sumsq(b_r_.p, m_, b_scal_.p, s);
-  launch_dense_gmax(b_gs_.p, b_scale_.p, x_, n_, b_scal_.p + 1, s);
-  if (tangent_) launch_dense_sumsq(x_, ng_, b_scal_.p + 2, s);  // |x|^2 over the ambient vector
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (has_loss_) launch_dense_sum(b_cterm_.p, m_, b_scal_.p + kSumSq, s); else launch_dense_sumsq(b_r_.p, m_, b_scal_.p + kSumSq, s);
+  launch_dense_gmax(b_gs_.p, b_scale_.p, x_, n_, b_scal_.p + kGradMax, s);  // (and |x|^2 behind it)
+  if (tangent_) launch_dense_sumsq(x_, ng_, b_scal_.p + kXSq, s);  // |x|^2 over the ambient vector
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kBlockFirst, b_scal_.p + kBlockFirst, (kBlockLast + 1 - kBlockFirst) * sizeof(double), hipMemcpyDeviceToHost, s));
   if (bounded_) {  // the gradient test is the projected gradient's
-    launch_dense_bounded_gmax(b_gs_.p, b_scale_.p, x_, b_bd_ambient_.p, b_bd_box_.p, b_bd_box_.p + ng_, n_, ng_, b_bd_scal_.p + 3, s);
-    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 40, b_bd_scal_.p + 3, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    launch_dense_bounded_gmax(b_gs_.p, b_scale_.p, x_, b_bd_ambient_.p, b_bd_box_.p, b_bd_box_.p + ng_, n_, ng_, b_bd_scal_.p + kBdGradMax, s);
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kBounds + kBdGradMax, b_bd_scal_.p + kBdGradMax, (kBdActive + 1 - kBdGradMax) * sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kFail, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
   SK_HIP_TRY(hipEventRecord(ev_[kEvJac], s));
   SK_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvJac]) == hipSuccess) phase_[0] += 1e-3 * ms;
-  int fail = 0; std::memcpy(&fail, h_scal_ + 16, sizeof(int));
-  cost_ = 0.5 * h_scal_[0]; gmax_ = h_scal_[1]; xnorm_ = std::sqrt(h_scal_[2]);
-  if (bounded_) { gmax_ = h_scal_[40]; active_bounds_ = (long)h_scal_[42]; }
-  if (fail || !std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
+  add_phases(0, 0);
+  cost_ = 0.5 * h_scal_[kSumSq]; gmax_ = h_scal_[kGradMax]; xnorm_ = std::sqrt(h_scal_[kXSq]);
+  if (bounded_) { gmax_ = h_scal_[kBounds + kBdGradMax]; active_bounds_ = (long)h_scal_[kBounds + kBdActive]; }
+  if (host_flag(kFail) || !std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
   return SK_OK;
 }
 
@@ -325,46 +336,68 @@ int DenseSolver::enqueue_linear_solve(double radius) {
   return SK_OK;
 }
 
-int DenseSolver::try_step(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
-  if (dogleg()) return try_step_dogleg(radius, valid, mcc, new_cost, step_norm);
+// The cost of the point in x_new_ and its distance from x, behind the launches that formed it: the evaluation, the reduction, the
+// copies of b_scal_'s block and of the failure flag, the one synchronisation, phases 3 and 4.  after_solve: the candidate is the
+// step of a linear solve (formed since kEvChol; that solve's info and ok flags come back too), else a trial's (formed since kEvBegin).
+// A candidate that cannot be evaluated costs +infinity.
+int DenseSolver::candidate_cost(bool after_solve, double* cost, double* step_norm) {
   hipStream_t s = stream_;
-  *valid = false;
+  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
+  int rc = evaluate(x_new_, false);
+  const bool eval_failed = rc == SK_ERR_EVALUATION_FAILED;
+  if (rc && !eval_failed) return rc;
+  if (has_loss_) { apply_loss(b_rc_.p, false); launch_dense_sum(b_cterm_.p, m_, b_scal_.p + kCandSumSq, s); }
+  else launch_dense_sumsq(b_rc_.p, m_, b_scal_.p + kCandSumSq, s);
+  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kBlockFirst, b_scal_.p + kBlockFirst, (kBlockLast + 1 - kBlockFirst) * sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kFail, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (after_solve) {
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kInfo, b_info_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kOk, b_ok_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  }
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  add_phases(3, 4, after_solve ? kEvChol : kEvBegin);
+  *cost = (host_flag(kFail) || eval_failed) ? std::numeric_limits<double>::infinity() : 0.5 * h_scal_[kCandSumSq];
+  *step_norm = std::sqrt(h_scal_[kStepSq]);
+  return SK_OK;
+}
+
+int DenseSolver::linear_solve(double radius, LinearSolve* out) {
+  hipStream_t s = stream_;
+  *out = LinearSolve();
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   int rc = enqueue_linear_solve(radius);
   if (rc) return rc;
-  if (tangent_) launch_dense_plus(b_y_.p, b_scale_.p, x_, b_step_.p, x_new_, b_pblocks_.p, num_pblocks_, b_scal_.p, s);
-  else launch_dense_step(b_y_.p, b_scale_.p, x_, b_step_.p, x_new_, n_, b_scal_.p, s);
-  launch_dense_model(b_J_.p, b_r_.p, b_step_.p, m_, n_, b_scal_.p + 1, s);
-  if (bounded_) {  // g . delta and max |delta_j| of the unconstrained step; the candidate becomes P(x + delta)
-    launch_dense_directional_derivative(b_gs_.p, b_step_.p, b_scale_.p, n_, b_bd_scal_.p + 1, s);
-    launch_dense_bounded_candidate(b_step_.p, b_scale_.p, x_, 1.0, tangent_ ? b_pblocks_.p : nullptr, num_pblocks_, b_bd_box_.p, b_bd_box_.p + ng_, x_new_, n_, b_scal_.p, s);
-    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 44, b_bd_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (dogleg()) {  // the vectors [s | g] and their eight scalars; the candidate is dogleg_trial's
+    double* sv = b_dl_vec_.p;
+    double* gv = b_dl_vec_.p + n_;
+    launch_dense_dogleg_vectors(b_colsq_.p, b_gs_.p, b_y_.p, n_, opt_.min_lm_diagonal, opt_.max_lm_diagonal, sv, gv, b_dl_scal_.p + kDlNorms, s);
+    launch_dense_dogleg_products(b_J_.p, b_r_.p, sv, gv, m_, n_, b_dl_scal_.p + kDlScalars, s);
+    SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kDogleg, b_dl_scal_.p + kDlScalars, (kDlStepSq - kDlScalars) * sizeof(double), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kInfo, b_info_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kOk, b_ok_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipStreamSynchronize(s));
+    add_phases(3, 3, kEvChol);
+  } else {
+    if (tangent_) launch_dense_plus(b_y_.p, b_scale_.p, x_, b_step_.p, x_new_, b_pblocks_.p, num_pblocks_, b_scal_.p + kStepSq, s);
+    else launch_dense_step(b_y_.p, b_scale_.p, x_, b_step_.p, x_new_, n_, b_scal_.p + kStepSq, s);
+    launch_dense_model(b_J_.p, b_r_.p, b_step_.p, m_, n_, b_scal_.p + kModel, s);
+    if (bounded_) {  // g . delta and max |delta_j| of the unconstrained step; the candidate becomes P(x + delta)
+      launch_dense_directional_derivative(b_gs_.p, b_step_.p, b_scale_.p, n_, b_bd_scal_.p + kBdGDelta, s);
+      launch_dense_bounded_candidate(b_step_.p, b_scale_.p, x_, 1.0, tangent_ ? b_pblocks_.p : nullptr, num_pblocks_, b_bd_box_.p, b_bd_box_.p + ng_, x_new_, n_, b_scal_.p + kStepSq, s);
+      SK_HIP_TRY(hipMemcpyAsync(h_scal_ + kBounds + kBdStepSq, b_bd_scal_.p + kBdStepSq, (kBdMaxDelta + 1 - kBdStepSq) * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    rc = candidate_cost(true, &out->cost, &out->step_norm);
+    if (rc) return rc;
   }
-  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
-  rc = evaluate(x_new_, false);
-  const bool eval_failed = rc == SK_ERR_EVALUATION_FAILED;
-  if (rc && !eval_failed) return rc;
-  if (has_loss_) { apply_loss(b_rc_.p, false); launch_dense_sum(b_cterm_.p, m_, b_scal_.p + 2, s); }
-  else launch_dense_sumsq(b_rc_.p, m_, b_scal_.p + 2, s);
-  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 17, b_info_.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 18, b_ok_.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvAssemble]) == hipSuccess) phase_[1] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvAssemble], ev_[kEvChol]) == hipSuccess) phase_[2] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvChol], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
-  int fail = 0, info = 0, ok = 1;
-  std::memcpy(&fail, h_scal_ + 16, sizeof(int)); std::memcpy(&info, h_scal_ + 17, sizeof(int)); std::memcpy(&ok, h_scal_ + 18, sizeof(int));
-  if (info || !ok || !std::isfinite(h_scal_[0]) || !std::isfinite(h_scal_[1])) return SK_OK;  // invalid step
-  *valid = true;
-  *step_norm = std::sqrt(h_scal_[0]);
-  *mcc = -h_scal_[1];
-  *new_cost = (fail || eval_failed) ? std::numeric_limits<double>::infinity() : 0.5 * h_scal_[2];
-  if (bounded_) return line_search(h_scal_[45], h_scal_[46], new_cost, step_norm);
+  add_phases(1, 2);
+  if (host_flag(kInfo) || !host_flag(kOk)) return SK_OK;  // invalid step
+  if (dogleg()) { out->valid = true; out->dl = dogleg::Scalars::from(h_scal_ + kDogleg); return SK_OK; }
+  if (!std::isfinite(h_scal_[kStepSq]) || !std::isfinite(h_scal_[kModel])) return SK_OK;  // invalid step
+  out->valid = true;
+  out->model_cost_change = -h_scal_[kModel];
+  out->g_delta = h_scal_[kBounds + kBdGDelta]; out->max_delta = h_scal_[kBounds + kBdMaxDelta];  // (of this solve under bounds only, where they are read)
   return SK_OK;
 }
 
@@ -373,83 +406,17 @@ int DenseSolver::bounded_trial(double alpha, double* cost, double* step_norm) {
   hipStream_t s = stream_;
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   SK_HIP_TRY(hipMemsetAsync(b_fail_.p, 0, sizeof(int), s));
-  launch_dense_bounded_candidate(b_step_.p, b_scale_.p, x_, alpha, tangent_ ? b_pblocks_.p : nullptr, num_pblocks_, b_bd_box_.p, b_bd_box_.p + ng_, x_new_, n_, b_scal_.p, s);
-  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
-  int rc = evaluate(x_new_, false);
-  const bool eval_failed = rc == SK_ERR_EVALUATION_FAILED;
-  if (rc && !eval_failed) return rc;
-  if (has_loss_) { apply_loss(b_rc_.p, false); launch_dense_sum(b_cterm_.p, m_, b_scal_.p + 2, s); }
-  else launch_dense_sumsq(b_rc_.p, m_, b_scal_.p + 2, s);
-  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
-  int fail = 0;
-  std::memcpy(&fail, h_scal_ + 16, sizeof(int));
-  *step_norm = std::sqrt(h_scal_[0]);
-  *cost = (fail || eval_failed) ? std::numeric_limits<double>::infinity() : 0.5 * h_scal_[2];
-  return SK_OK;
+  launch_dense_bounded_candidate(b_step_.p, b_scale_.p, x_, alpha, tangent_ ? b_pblocks_.p : nullptr, num_pblocks_, b_bd_box_.p, b_bd_box_.p + ng_, x_new_, n_, b_scal_.p + kStepSq, s);
+  return candidate_cost(false, cost, step_norm);
 }
 
-int DenseSolver::try_step_dogleg(double radius, bool* valid, double* mcc, double* new_cost, double* step_norm) {
+// The DOGLEG candidate x + (a s + b g) scale from the vectors of the last linear solve (no tangent-space blocks: setup() refuses those).
+int DenseSolver::dogleg_trial(double a, double b, double* cost, double* step_norm) {
   hipStream_t s = stream_;
-  *valid = false;
-  float ms = 0.f;
-  double* sv = b_dl_vec_.p;
-  double* gv = b_dl_vec_.p + n_;
-  if (!dl_reuse_) {
-    bool solved = false;
-    while (dl_mu_ < dogleg::kMaxMu) {
-      SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
-      int rc = enqueue_linear_solve(1.0 / dl_mu_);
-      if (rc) return rc;
-      launch_dense_dogleg_vectors(b_colsq_.p, b_gs_.p, b_y_.p, n_, opt_.min_lm_diagonal, opt_.max_lm_diagonal, sv, gv, b_dl_scal_.p + 5, s);
-      launch_dense_dogleg_products(b_J_.p, b_r_.p, sv, gv, m_, n_, b_dl_scal_.p, s);
-      SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
-      SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 24, b_dl_scal_.p, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-      SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 17, b_info_.p, sizeof(int), hipMemcpyDeviceToHost, s));
-      SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 18, b_ok_.p, sizeof(int), hipMemcpyDeviceToHost, s));
-      SK_HIP_TRY(hipStreamSynchronize(s));
-      if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvAssemble]) == hipSuccess) phase_[1] += 1e-3 * ms;
-      if (hipEventElapsedTime(&ms, ev_[kEvAssemble], ev_[kEvChol]) == hipSuccess) phase_[2] += 1e-3 * ms;
-      if (hipEventElapsedTime(&ms, ev_[kEvChol], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
-      int info = 0, ok = 1;
-      std::memcpy(&info, h_scal_ + 17, sizeof(int)); std::memcpy(&ok, h_scal_ + 18, sizeof(int));
-      if (!info && ok) { solved = true; break; }
-      dl_mu_ *= dogleg::kMuIncreaseFactor;
-    }
-    if (!solved) return SK_OK;  // invalid step
-    dl_k_ = dogleg::Scalars::from(h_scal_ + 24);
-  } else {
-    ++n_dl_reused_;
-  }
-  if (!dogleg::interpolate(dl_k_, radius, &dl_a_, &dl_b_, &dl_step_norm_, mcc)) return SK_OK;
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   SK_HIP_TRY(hipMemsetAsync(b_fail_.p, 0, sizeof(int), s));
-  launch_dense_dogleg_combine(sv, gv, dl_a_, dl_b_, b_scale_.p, x_, b_step_.p, x_new_, n_, b_dl_scal_.p + 8, s);
-  SK_HIP_TRY(hipEventRecord(ev_[kEvBacksub], s));
-  int rc = evaluate(x_new_, false);
-  const bool eval_failed = rc == SK_ERR_EVALUATION_FAILED;
-  if (rc && !eval_failed) return rc;
-  if (has_loss_) { apply_loss(b_rc_.p, false); launch_dense_sum(b_cterm_.p, m_, b_scal_.p + 2, s); }
-  else launch_dense_sumsq(b_rc_.p, m_, b_scal_.p + 2, s);
-  SK_HIP_TRY(hipEventRecord(ev_[kEvCost], s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 2, b_scal_.p + 2, sizeof(double), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 32, b_dl_scal_.p + 8, sizeof(double), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipMemcpyAsync(h_scal_ + 16, b_fail_.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  if (hipEventElapsedTime(&ms, ev_[kEvBegin], ev_[kEvBacksub]) == hipSuccess) phase_[3] += 1e-3 * ms;
-  if (hipEventElapsedTime(&ms, ev_[kEvBacksub], ev_[kEvCost]) == hipSuccess) phase_[4] += 1e-3 * ms;
-  int fail = 0;
-  std::memcpy(&fail, h_scal_ + 16, sizeof(int));
-  if (!std::isfinite(h_scal_[32])) return SK_OK;  // invalid step
-  *valid = true;
-  *step_norm = std::sqrt(h_scal_[32]);
-  *new_cost = (fail || eval_failed) ? std::numeric_limits<double>::infinity() : 0.5 * h_scal_[2];
-  return SK_OK;
+  launch_dense_dogleg_combine(b_dl_vec_.p, b_dl_vec_.p + n_, a, b, b_scale_.p, x_, b_step_.p, x_new_, n_, b_scal_.p + kStepSq, s);
+  return candidate_cost(false, cost, step_norm);
 }
 
 int DenseSolver::write_back() {

@@ -1,4 +1,6 @@
-// Host-side trust-region loop shared by the Schur and the dense paths.
+// Host-side trust-region loop shared by the Schur and the dense paths: the iteration (step), the control flow of the three
+// strategies below it (try_step, line_search), the phase accounting.  A solver supplies device work through linear_solve,
+// dogleg_trial and bounded_trial (solver.hpp).
 #include "solver.hpp"
 
 #include <cmath>
@@ -108,6 +110,15 @@ int SolverBase::init_device() {
   return SK_OK;
 }
 
+void SolverBase::add_phase(int i, hipEvent_t from, hipEvent_t to) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, from, to) == hipSuccess) phase_[i] += 1e-3 * ms;
+  else (void)hipGetLastError();
+}
+void SolverBase::add_phases(int first, int last, int since) {
+  for (int i = first; i <= last; ++i) { add_phase(i, ev_[since], ev_[i + 1]); since = i + 1; }
+}
+
 // The hook runs on the solver's stream and the solver goes on enqueueing behind it: NO host synchronisation here (until round 5 every
 // collective ended in one — four per iteration of a segmented world, the device idle while the host caught up with its launches).  The
 // time of the all-reduce phase comes from event pairs that are read once they have completed (here, opportunistically, and in finish()).
@@ -116,9 +127,7 @@ void SolverBase::collect_allreduce_time(bool all) {
   for (; done + 1 < ar_pending_.size(); done += 2) {
     if (!all && hipEventQuery(ar_pending_[done + 1]) != hipSuccess) { (void)hipGetLastError(); break; }
     if (all) (void)hipEventSynchronize(ar_pending_[done + 1]);
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ar_pending_[done], ar_pending_[done + 1]) == hipSuccess) phase_[5] += 1e-3 * ms;
-    else (void)hipGetLastError();
+    add_phase(5, ar_pending_[done], ar_pending_[done + 1]);
     ar_free_.push_back(ar_pending_[done]); ar_free_.push_back(ar_pending_[done + 1]);
   }
   ar_pending_.erase(ar_pending_.begin(), ar_pending_.begin() + (long)done);
@@ -227,7 +236,7 @@ int SolverBase::check_bounds() {
 }
 
 // The line search of an iteration under bounds (common.hpp: namespace bounds) on phi(alpha) = cost(P(x + alpha delta)), f0 = cost_.
-// In: *cost = phi(1) and *step_norm of the candidate try_step has formed.  Out: those of the alpha that was kept (ls_alpha_), the
+// In: *cost = phi(1) and *step_norm of the candidate the linear solve has formed.  Out: those of the alpha that was kept (ls_alpha_), the
 // candidate buffers holding its point.  A search that fails keeps alpha = 1, as Ceres leaves delta alone.
 int SolverBase::line_search(double g0, double max_delta, double* cost, double* step_norm) {
   ls_alpha_ = 1.0; ls_evals_ = 1; ++n_ls_evals_;
@@ -256,6 +265,40 @@ int SolverBase::line_search(double g0, double max_delta, double* cost, double* s
     ++ls_evals_; ++n_ls_evals_;
   }
   ls_alpha_ = alpha; *cost = phi; *step_norm = norm;
+  return SK_OK;
+}
+
+// One candidate for this radius: valid (a step could be formed), the model's cost change, the candidate's cost, |x - candidate|.
+// Levenberg-Marquardt: one linear solve, the candidate and its cost fused into it.  Bounds: the same solve — the unconstrained step
+// and its model — then the line search over P(x + alpha delta).  DOGLEG: after a new Jacobian the Gauss-Newton solve at the current
+// mu, again at ten times mu while the damped system is not positive definite (each solve counts in "linear_solves"); then, and
+// after every rejected step (dl_reuse_), the candidate of this radius from the two vectors the solve left on the device.
+int SolverBase::try_step(double radius, bool* valid, double* model_cost_change, double* new_cost, double* step_norm) {
+  *valid = false;
+  LinearSolve solve;
+  if (!dogleg()) {
+    int rc = linear_solve(radius, &solve);
+    if (rc || !solve.valid) return rc;
+    *valid = true;
+    *model_cost_change = solve.model_cost_change; *new_cost = solve.cost; *step_norm = solve.step_norm;
+    return bounded_ ? line_search(solve.g_delta, solve.max_delta, new_cost, step_norm) : SK_OK;
+  }
+  if (dl_reuse_) {
+    ++n_dl_reused_;
+  } else {
+    while (dl_mu_ < dogleg::kMaxMu) {
+      int rc = linear_solve(1.0 / dl_mu_, &solve);
+      if (rc) return rc;
+      if (solve.valid) break;
+      dl_mu_ *= dogleg::kMuIncreaseFactor;
+    }
+    if (!solve.valid) return SK_OK;  // invalid step
+    dl_k_ = solve.dl;
+  }
+  if (!dogleg::interpolate(dl_k_, radius, &dl_a_, &dl_b_, &dl_step_norm_, model_cost_change)) return SK_OK;
+  int rc = dogleg_trial(dl_a_, dl_b_, new_cost, step_norm);
+  if (rc) return rc;
+  *valid = std::isfinite(*step_norm);
   return SK_OK;
 }
 

@@ -1,4 +1,4 @@
-// Trust-region Levenberg-Marquardt driver (host) over device linear algebra.
+// Trust-region driver (host) over device linear algebra: the loop and the control flow of every strategy, written once.
 // Restates the loop native Ceres [ext] runs behind `ceres.solve`
 // (EX/SimpleBundleAdjuster.scala:152, EX/CurveFitting.scala:127); constants and
 // update rules as published for Ceres 1.x.  Only a
@@ -18,6 +18,33 @@
 #include "common.hpp"
 
 namespace sk {
+
+// What the strategy kernels leave in their scalar buffers (bal_kernels.hpp: DoglegDev::scal, BoundsDev::scal; the dense kernels write
+// the same layouts), as offsets into those buffers and into the pinned regions that mirror them.
+enum DoglegScal {
+  kDlScalars = 0,  // the eight dogleg::Scalars in the kernels' order: the observation products ...
+  kDlNorms = 5,    // ... and the vector norms |g_hat|^2, g_hat . p, |p|^2
+  kDlStepSq = 8,   // |x - x_new|^2 of the last combined step
+  kDlScalCount
+};
+enum BoundsScal {
+  kBdStepSq = 0,  // |x - x_new|^2 of the last candidate
+  kBdGDelta,      // g . delta of the unconstrained step
+  kBdMaxDelta,    // max_j |delta_j|
+  kBdGradMax,     // max_j |x_j - P(x_j - g_j)|: the gradient test under bounds
+  kBdXSq,         // |x|^2
+  kBdActive,      // coordinates of x on a bound
+  kBdScalCount
+};
+
+// What one linear solve leaves on the host (SolverBase::linear_solve); a field is set where the strategy forms it.
+struct LinearSolve {
+  bool valid = false;                  // the system was positive definite and the scalars are finite
+  double model_cost_change = 0.0;      // of the step at this radius (LM, bounds)
+  double cost = 0.0, step_norm = 0.0;  // of the candidate formed behind the back-substitution (LM, bounds)
+  double g_delta = 0.0, max_delta = 0.0;  // bounds: what the line search starts from
+  dogleg::Scalars dl;                  // DOGLEG
+};
 
 class SolverBase {
  public:
@@ -48,17 +75,24 @@ class SolverBase {
   // --- representation-specific pieces -------------------------------------
   virtual int setup() = 0;                        // build device structures, upload x
   virtual int evaluate_with_jacobian(bool first) = 0;  // at current x: cost_, gmax_, xnorm_
-  // D from radius, solve, candidate point, candidate cost:
-  virtual int try_step(double radius, bool* valid, double* model_cost_change, double* new_cost, double* step_norm) = 0;
+  // The device work of one trust-region iteration.  SolverBase::try_step owns the control flow of every strategy (Levenberg-Marquardt,
+  // bounds, DOGLEG); a solver enqueues launches and reads scalars back.  linear_solve: D from the radius, the factorisation, the
+  // back-substitution and what the strategy needs behind it — the candidate x + delta and its cost (LM); the candidate P(x + delta),
+  // its cost, g . delta and max_j |delta_j| (bounded_); the two vectors s and g and their eight scalars, no candidate (dogleg()).
+  // Every enqueued factorisation counts in n_linear_solves_.
+  virtual int linear_solve(double radius, LinearSolve* out) = 0;
+  // the candidate a s + b g from the vectors of the last linear solve, its cost, |x - candidate| (not finite: no step)
+  virtual int dogleg_trial(double a, double b, double* cost, double* step_norm) { (void)a; (void)b; (void)cost; (void)step_norm; return SK_ERR_UNSUPPORTED; }
+  // the candidate P(x + alpha delta) from the step of the last linear solve, its cost, |x - candidate|
+  virtual int bounded_trial(double alpha, double* cost, double* step_norm) { (void)alpha; (void)cost; (void)step_norm; return SK_ERR_UNSUPPORTED; }
   virtual void accept_candidate() = 0;            // x <- candidate (pointer swap)
   virtual int write_back() = 0;                   // device x -> caller memory
   virtual void describe(Summary* s) = 0;
-  virtual bool supports_dogleg() const { return false; }  // try_step honours dl_reuse_ / dl_mu_ and sets dl_step_norm_
+  virtual bool supports_dogleg() const { return false; }  // linear_solve fills LinearSolve::dl, dogleg_trial is implemented
   // Parameter bounds (bounded_: the problem has a finite bound).  refuses_bounds: why this solver cannot take this problem's
-  // bounds, or nullptr.  try_step then forms the candidate P(x + delta), leaves g0 = g . delta and max_j |delta_j| to
-  // line_search, which asks for every further trial through bounded_trial (candidate of alpha, its cost, |x - candidate|).
+  // bounds, or nullptr.
   virtual const char* refuses_bounds() const { return "parameter bounds are implemented for DENSE_SCHUR and for DENSE_QR / DENSE_NORMAL_CHOLESKY over residual blocks (not supported on dense-row problems)"; }
-  virtual int bounded_trial(double alpha, double* cost, double* step_norm) { (void)alpha; (void)cost; (void)step_norm; return SK_ERR_UNSUPPORTED; }
+  int try_step(double radius, bool* valid, double* model_cost_change, double* new_cost, double* step_norm);
   int line_search(double g0, double max_delta, double* cost, double* step_norm);
   int check_bounds();  // create(): the refusals, the feasibility of the box
   bool bounded_ = false, infeasible_ = false;
@@ -71,6 +105,10 @@ class SolverBase {
   double now() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0_).count(); }
   void log_iteration(int it, double cost_change, double step_norm, double rho, int valid, int success, double iter_time);
   int allreduce(double* dev, size_t count);
+  void add_phase(int i, hipEvent_t from, hipEvent_t to);  // phase_[i] += the time between two events that have completed
+  // ... for the phases first..last of one enqueued sequence: phase i ends at ev_[i + 1] (kEvJac ... kEvCost) and begins where the one
+  // before it ended, the first of them at ev_[since]
+  void add_phases(int first, int last, int since = kEvBegin);
   void collect_allreduce_time(bool all);  // phase_[5] from the event pairs of collectives that have completed (all: wait for every one)
   std::vector<hipEvent_t> ar_pending_, ar_free_;
 
@@ -88,8 +126,8 @@ class SolverBase {
   double radius_ = 0, decrease_factor_ = 2.0;
   int iteration_ = 0, invalid_ = 0, n_success_ = 0, n_unsuccess_ = 0;
   bool terminated_ = false;
-  // DOGLEG state (common.hpp: namespace dogleg).  try_step sets dl_step_norm_ (the step's norm in the diagonal-scaled space) and
-  // honours dl_reuse_ (the Jacobian has not changed since the last linear solve: interpolate again, solve nothing)
+  // DOGLEG state (common.hpp: namespace dogleg).  dl_step_norm_: the step's norm in the diagonal-scaled space; dl_reuse_: the Jacobian
+  // has not changed since the last linear solve (try_step interpolates again and solves nothing)
   double dl_mu_ = dogleg::kMinMu, dl_step_norm_ = 0.0;
   bool dl_reuse_ = false;
   long n_linear_solves_ = 0, n_dl_reused_ = 0;  // factorisations enqueued; iterations that re-interpolated (sk_solver_stat)
