@@ -88,6 +88,16 @@ public final class SkeresNative {
   public static native int skProblemNumParameterBlocks(long p);
   public static native int skProblemNumParameters(long p);
   public static native int skProblemNumResiduals(long p);
+  // ceres::Problem::Evaluate (ceres/problem.h, ceres/crs_matrix.h via ceres.i); options may be 0 (defaults), output arrays null
+  public static native long skEvaluateOptionsNew();
+  public static native void skEvaluateOptionsFree(long o);
+  public static native int skEvaluateOptionsSetApplyLossFunction(long o, int on);
+  public static native int skEvaluateOptionsSetDevice(long o, int device);
+  public static native int skEvaluateOptionsSetResidualBlocks(long o, int[] ids);
+  public static native int skEvaluateOptionsSetParameterBlocks(long o, long[] blocks);
+  public static native int skProblemEvaluateSizes(long p, long o, long[] sizes);
+  public static native int skProblemEvaluateStructure(long p, long o, int[] rows, int[] cols);
+  public static native int skProblemEvaluate(long p, long o, double[] cost, double[] residuals, double[] gradient, double[] values);
   // Solver.Options
   public static native long skOptionsNew();
   public static native void skOptionsFree(long o);

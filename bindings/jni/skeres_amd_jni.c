@@ -374,3 +374,70 @@ SK_JNI(jint, skRotationApply)(JNIEnv* env, jclass c, jint op, jboolean row_major
   (*env)->ReleaseDoubleArrayElements(env, in, pi, JNI_ABORT);
   return check(env, rc);
 }
+
+/* ---- Problem::Evaluate (ceres/problem.h, ceres/crs_matrix.h via ceres.i): CeresProblem.evaluate in Native.scala ---------------- */
+SK_JNI(jlong, skEvaluateOptionsNew)(JNIEnv* env, jclass c) { (void)c; return check_handle(env, sk_evaluate_options_new()); }
+SK_JNI(void, skEvaluateOptionsFree)(JNIEnv* env, jclass c, jlong o) { (void)env; (void)c; sk_evaluate_options_free(PTR(sk_evaluate_options, o)); }
+SK_JNI(jint, skEvaluateOptionsSetApplyLossFunction)(JNIEnv* env, jclass c, jlong o, jint on) { (void)c; return check(env, sk_evaluate_options_set_apply_loss_function(PTR(sk_evaluate_options, o), on)); }
+SK_JNI(jint, skEvaluateOptionsSetDevice)(JNIEnv* env, jclass c, jlong o, jint device) { (void)c; return check(env, sk_evaluate_options_set_device(PTR(sk_evaluate_options, o), device)); }
+SK_JNI(jint, skEvaluateOptionsSetResidualBlocks)(JNIEnv* env, jclass c, jlong o, jintArray ids) {
+  (void)c;
+  const jsize n = (*env)->GetArrayLength(env, ids);
+  jint* p = (*env)->GetIntArrayElements(env, ids, NULL);
+  const int rc = sk_evaluate_options_set_residual_blocks(PTR(sk_evaluate_options, o), (const sk_residual_block_id*)p, (int)n);
+  (*env)->ReleaseIntArrayElements(env, ids, p, JNI_ABORT);
+  return check(env, rc);
+}
+/* blocks: the native addresses of the parameter blocks (DoubleArray / DoubleArraySlice pointers) */
+SK_JNI(jint, skEvaluateOptionsSetParameterBlocks)(JNIEnv* env, jclass c, jlong o, jlongArray blocks) {
+  (void)c;
+  const jsize n = (*env)->GetArrayLength(env, blocks);
+  jlong* p = (*env)->GetLongArrayElements(env, blocks, NULL);
+  double** ptrs = (double**)malloc(sizeof(double*) * (size_t)(n ? n : 1));
+  int rc = SK_ERR_HIP;
+  if (ptrs) {
+    for (jsize i = 0; i < n; ++i) ptrs[i] = PTR(double, p[i]);
+    rc = sk_evaluate_options_set_parameter_blocks(PTR(sk_evaluate_options, o), ptrs, (int)n);
+    free(ptrs);
+  }
+  (*env)->ReleaseLongArrayElements(env, blocks, p, JNI_ABORT);
+  return check(env, rc);
+}
+/* sizes: long[3] = (num_rows, num_cols, num_nonzeros) */
+SK_JNI(jint, skProblemEvaluateSizes)(JNIEnv* env, jclass c, jlong p, jlong o, jlongArray sizes) {
+  (void)c;
+  int rows = 0, cols = 0;
+  long long nnz = 0;
+  const int rc = sk_problem_evaluate_sizes(PTR(sk_problem, p), PTR(sk_evaluate_options, o), &rows, &cols, &nnz);
+  if (rc == SK_OK) {
+    jlong* s = (*env)->GetLongArrayElements(env, sizes, NULL);
+    s[0] = rows; s[1] = cols; s[2] = (jlong)nnz;
+    (*env)->ReleaseLongArrayElements(env, sizes, s, 0);
+  }
+  return check(env, rc);
+}
+SK_JNI(jint, skProblemEvaluateStructure)(JNIEnv* env, jclass c, jlong p, jlong o, jintArray rows, jintArray cols) {
+  (void)c;
+  jint* r = (*env)->GetIntArrayElements(env, rows, NULL);
+  jint* k = (*env)->GetIntArrayElements(env, cols, NULL);
+  const int rc = sk_problem_evaluate_structure(PTR(sk_problem, p), PTR(sk_evaluate_options, o), (int*)r, (int*)k);
+  (*env)->ReleaseIntArrayElements(env, cols, k, rc == SK_OK ? 0 : JNI_ABORT);
+  (*env)->ReleaseIntArrayElements(env, rows, r, rc == SK_OK ? 0 : JNI_ABORT);
+  return check(env, rc);
+}
+/* every output array may be null; cost is a double[1].  Director upcalls (host-callback blocks) arrive on this thread. */
+SK_JNI(jint, skProblemEvaluate)(JNIEnv* env, jclass c, jlong p, jlong o, jdoubleArray cost, jdoubleArray residuals, jdoubleArray gradient, jdoubleArray values) {
+  (void)c;
+  jdouble* pc = cost ? (*env)->GetDoubleArrayElements(env, cost, NULL) : NULL;
+  jdouble* pr = residuals ? (*env)->GetDoubleArrayElements(env, residuals, NULL) : NULL;
+  jdouble* pg = gradient ? (*env)->GetDoubleArrayElements(env, gradient, NULL) : NULL;
+  jdouble* pv = values ? (*env)->GetDoubleArrayElements(env, values, NULL) : NULL;
+  const int rc = sk_problem_evaluate(PTR(sk_problem, p), PTR(sk_evaluate_options, o), pc, pr, pg, pv);
+  const jint mode = rc == SK_OK ? 0 : JNI_ABORT;
+  if (pv) (*env)->ReleaseDoubleArrayElements(env, values, pv, mode);
+  if (pg) (*env)->ReleaseDoubleArrayElements(env, gradient, pg, mode);
+  if (pr) (*env)->ReleaseDoubleArrayElements(env, residuals, pr, mode);
+  if (pc) (*env)->ReleaseDoubleArrayElements(env, cost, pc, mode);
+  if ((*env)->ExceptionCheck(env)) return (jint)rc;  /* an evaluate() upcall threw: let that exception propagate */
+  return check(env, rc);
+}

@@ -153,9 +153,46 @@ class CeresProblem(options: CeresProblem.Options) {
   def numParameterBlocks: Int = SkeresNative.skProblemNumParameterBlocks(handle)
   def numParameters: Int = SkeresNative.skProblemNumParameters(handle)
   def numResiduals: Int = SkeresNative.skProblemNumResiduals(handle)
+  /** ceres::Problem::Evaluate (ceres/problem.h via ceres.i) at the current contents of the parameter memory, on the device: the cost,
+    * and — where the caller passes an array of the right length, or asks for it — residuals, gradient and the Jacobian as a CRSMatrix.
+    * Rows follow evalOptions' residual blocks (all, in the order added), columns its parameter blocks (all, in the order first seen),
+    * each with its tangent size; a constant block keeps its columns and stores nothing. */
+  def evaluate(evalOptions: CeresProblem.EvaluateOptions, wantResiduals: Boolean, wantGradient: Boolean, wantJacobian: Boolean): CeresProblem.Evaluation = {
+    val o = if (evalOptions == null) 0L else evalOptions.handle
+    val sizes = new Array[Long](3)
+    SkeresNative.skProblemEvaluateSizes(handle, o, sizes)
+    val cost = new Array[Double](1)
+    val residuals = if (wantResiduals) new Array[Double](sizes(0).toInt) else null
+    val gradient = if (wantGradient) new Array[Double](sizes(1).toInt) else null
+    val jacobian = if (wantJacobian) evaluateStructure(evalOptions) else null
+    SkeresNative.skProblemEvaluate(handle, o, cost, residuals, gradient, if (jacobian == null) null else jacobian.values)
+    new CeresProblem.Evaluation(cost(0), residuals, gradient, jacobian)
+  }
+  def evaluate(evalOptions: CeresProblem.EvaluateOptions): CeresProblem.Evaluation = evaluate(evalOptions, true, true, true)
+  /** The CRSMatrix evaluate would fill, its values zero: host logic, no device needed. */
+  def evaluateStructure(evalOptions: CeresProblem.EvaluateOptions): CRSMatrix = {
+    val o = if (evalOptions == null) 0L else evalOptions.handle
+    val sizes = new Array[Long](3)
+    SkeresNative.skProblemEvaluateSizes(handle, o, sizes)
+    val m = new CRSMatrix(sizes(0).toInt, sizes(1).toInt, new Array[Int](sizes(0).toInt + 1), new Array[Int](sizes(2).toInt), new Array[Double](sizes(2).toInt))
+    SkeresNative.skProblemEvaluateStructure(handle, o, m.rows, m.cols)
+    m
+  }
   override def finalize(): Unit = SkeresNative.skProblemFree(handle)
 }
+/** ceres::CRSMatrix (ceres/crs_matrix.h via ceres.i): row r holds cols / values [rows(r), rows(r + 1)). */
+class CRSMatrix(val numRows: Int, val numCols: Int, val rows: Array[Int], val cols: Array[Int], val values: Array[Double])
 object CeresProblem {
+  /** ceres::Problem::EvaluateOptions; empty lists mean all; num_threads has no counterpart. */
+  class EvaluateOptions {
+    val handle: Long = SkeresNative.skEvaluateOptionsNew()
+    def setApplyLossFunction(on: Boolean): Unit = SkeresNative.skEvaluateOptionsSetApplyLossFunction(handle, if (on) 1 else 0)
+    def setResidualBlocks(ids: Array[Int]): Unit = SkeresNative.skEvaluateOptionsSetResidualBlocks(handle, ids)
+    def setParameterBlocks(blocks: Seq[DoublePointer]): Unit = SkeresNative.skEvaluateOptionsSetParameterBlocks(handle, blocks.map(_.address).toArray)
+    def setDevice(device: Int): Unit = SkeresNative.skEvaluateOptionsSetDevice(handle, device)
+    override def finalize(): Unit = SkeresNative.skEvaluateOptionsFree(handle)
+  }
+  class Evaluation(val cost: Double, val residuals: Array[Double], val gradient: Array[Double], val jacobian: CRSMatrix)
   /** The native problem never owns cost or loss functions (sk_problem_new): the setters exist for source compatibility. */
   class Options { def setCostFunctionOwnership(o: Ownership.Value): Unit = (); def setLossFunctionOwnership(o: Ownership.Value): Unit = () }
 }

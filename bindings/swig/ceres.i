@@ -51,6 +51,8 @@ void initGoogleLogging(const char* name) { sk_init_logging(name); }
 // (sk_options_set_trust_region_strategy_type / sk_options_set_dogleg_type, their two getters and their two enums come through this %include, as the
 // reference's come through ceres/types.h and ceres/solver.h, ceres.i:137,151)
 // (sk_problem_set_parameter_lower_bound / _upper_bound and their getters too, as the reference's come through ceres/problem.h, ceres.i:150)
+// (sk_evaluate_options_* and sk_problem_evaluate / _sizes / _structure too: ceres::Problem::Evaluate and ceres::CRSMatrix, which the reference's
+// ceres.i %include's with ceres/problem.h and ceres/crs_matrix.h; CeresProblem.evaluate in Native.scala binds them by hand over Java arrays)
 %include "skeres_amd.h"
 
 // load the native libraries as the reference's module class does (ceres.i:213-223)

@@ -333,6 +333,51 @@ int sk_problem_num_parameter_blocks(const sk_problem* p);  /* Problem::NumParame
 int sk_problem_num_parameters(const sk_problem* p);        /* Problem::NumParameters */
 int sk_problem_num_residuals(const sk_problem* p);         /* Problem::NumResiduals */
 
+/* ---- Problem::Evaluate: ceres::Problem::Evaluate(EvaluateOptions, cost, residuals, gradient, CRSMatrix*) -----------------
+ * ceres/problem.h and ceres/crs_matrix.h, both %include'd by ceres.i; inherited by CORE/Problem.scala:16.  Cost, residuals,
+ * gradient and the Jacobian in compressed-row form at the CURRENT contents of the caller's parameter memory (bounds play no part).
+ * The semantics are Ceres 1.x's, restated from memory like the rest of the minimiser:
+ *   rows      the residual blocks of the list, in list order (no list: in the order added), num_residuals rows each — whatever
+ *             order the kernels evaluate them in;
+ *   columns   the parameter blocks of the list, in list order (no list: in the order first seen), each with its tangent size: the
+ *             local size of its parameterization, else its size.  A block absent from a given list is held constant for the call and
+ *             has no columns.  A block that is constant (sk_problem_set_parameter_block_constant) and listed (or present, with no
+ *             list) KEEPS its columns but has no stored entries and a zero gradient — unlike the solvers, whose internal convention
+ *             is local size 0 for a constant block;
+ *   loss      apply_loss_function on (the default) and a block with a loss: cost = 1/2 sum rho(|r_b|^2), residuals and Jacobian
+ *             corrected as the solvers' corrector does it (residuals whenever they are asked for); off, or no loss: the plain r, J
+ *             and 1/2 sum |r|^2;
+ *   Jacobian  per residual block and non-constant parameter block the dense num_residuals x tangent size block
+ *             J_global * dPlus/ddelta (subset: a column selection), every entry stored, zeros included; within a row the columns
+ *             ascend strictly, so a residual block whose parameter blocks are not in column order has its blocks permuted.  rows /
+ *             cols are 32-bit as in ceres::CRSMatrix: a matrix with 2^31 entries or more is SK_ERR_UNSUPPORTED;
+ *   gradient  J^T r of exactly that matrix and those residuals (so it follows apply_loss_function), summed in a fixed order:
+ *             two calls on the same inputs return the same bytes.
+ * Device functors, recorded functors and host-callback blocks (evaluated on the host through their sk_evaluate_fn) are all taken;
+ * nothing depends on a linear solver type, a block shape or a world of ranks: one device.  EvaluateOptions::num_threads has no
+ * counterpart.  Errors: SK_ERR_INVALID_ARGUMENT — an id out of range or listed twice, a pointer that is no parameter block of the
+ * problem or is listed twice; SK_ERR_NO_DEVICE — sk_problem_evaluate without a GPU (the two host-only calls need none);
+ * SK_ERR_EVALUATION_FAILED — a functor or callback reported failure (outputs unspecified); SK_ERR_UNSUPPORTED — a problem with
+ * dense rows (sk_problem_add_dense_rows), whose Jacobian is dense by construction. */
+typedef struct sk_evaluate_options sk_evaluate_options;      /* ceres::Problem::EvaluateOptions */
+sk_evaluate_options* sk_evaluate_options_new(void);          /* all parameter blocks, all residual blocks, apply_loss_function = 1, current device */
+void sk_evaluate_options_free(sk_evaluate_options* o);
+int sk_evaluate_options_set_apply_loss_function(sk_evaluate_options* o, int on);
+int sk_evaluate_options_set_residual_blocks(sk_evaluate_options* o, const sk_residual_block_id* ids, int n);   /* n == 0: all, in the order added */
+int sk_evaluate_options_set_parameter_blocks(sk_evaluate_options* o, double* const* blocks, int n);           /* n == 0: all, in the order first seen */
+int sk_evaluate_options_set_device(sk_evaluate_options* o, int hip_device);
+/* (no reference counterpart) on != 0: sk_problem_evaluate records HIP events around its phases, and _launch_seconds returns the
+ * device seconds of the last call's phase: 0 uploads, 1 evaluation launches (with the host callbacks), 2 finish, 3 gradient,
+ * 4 cost, 5 downloads. */
+int sk_evaluate_options_set_launch_timing(sk_evaluate_options* o, int on);
+double sk_evaluate_options_launch_seconds(const sk_evaluate_options* o, int phase);
+/* host data alone, no device needed */
+int sk_problem_evaluate_sizes(const sk_problem* p, const sk_evaluate_options* o, int* num_rows, int* num_cols, long long* num_nonzeros);
+int sk_problem_evaluate_structure(const sk_problem* p, const sk_evaluate_options* o, int* rows /* num_rows + 1 */, int* cols /* num_nonzeros */);
+/* on the device; every output may be NULL; o may be NULL (defaults) */
+int sk_problem_evaluate(sk_problem* p, const sk_evaluate_options* o, double* cost, double* residuals /* num_rows */,
+                        double* gradient /* num_cols */, double* jacobian_values /* num_nonzeros */);
+
 /* ---- Solver.Options (setters are ceres.i:89-92 lowerCamelCase renames) ---- */
 sk_options* sk_options_new(void);                    /* Ceres 1.x defaults, SURVEY.md §8a row a13 */
 void sk_options_free(sk_options* o);

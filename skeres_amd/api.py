@@ -172,6 +172,17 @@ _SIGS = {
     "sk_synth_dense_targets": (C.c_int, [C.c_double, C.c_int, C.c_int, _dp, _dp]),
     "sk_problem_point_partition": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _ip, _ip]),
     "sk_problem_segment_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, _ip, _ip]),
+    "sk_evaluate_options_new": (C.c_void_p, []),
+    "sk_evaluate_options_free": (None, [C.c_void_p]),
+    "sk_evaluate_options_set_apply_loss_function": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_evaluate_options_set_residual_blocks": (C.c_int, [C.c_void_p, _ip, C.c_int]),
+    "sk_evaluate_options_set_parameter_blocks": (C.c_int, [C.c_void_p, _dpp, C.c_int]),
+    "sk_evaluate_options_set_device": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_evaluate_options_set_launch_timing": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_evaluate_options_launch_seconds": (C.c_double, [C.c_void_p, C.c_int]),
+    "sk_problem_evaluate_sizes": (C.c_int, [C.c_void_p, C.c_void_p, _ip, _ip, C.POINTER(C.c_longlong)]),
+    "sk_problem_evaluate_structure": (C.c_int, [C.c_void_p, C.c_void_p, _ip, _ip]),
+    "sk_problem_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, _dp, _dp]),
 }
 
 
@@ -970,9 +981,60 @@ class TerminationType:
     CONVERGENCE, NO_CONVERGENCE, FAILURE, USER_SUCCESS, USER_FAILURE = range(5)
 
 
+class CRSMatrix:
+    """ceres::CRSMatrix (ceres/crs_matrix.h via ceres.i): row r holds cols[rows[r]:rows[r + 1]] / values[rows[r]:rows[r + 1]];
+    numpy arrays (rows, cols: int32; values: float64, None where only the structure was asked for)."""
+
+    def __init__(self, num_rows, num_cols, rows, cols, values=None):
+        self.num_rows, self.num_cols, self.rows, self.cols, self.values = int(num_rows), int(num_cols), rows, cols, values
+
+    def toDense(self):
+        out = np.zeros((self.num_rows, self.num_cols))
+        for r in range(self.num_rows):
+            a, b = self.rows[r], self.rows[r + 1]
+            out[r, self.cols[a:b]] = self.values[a:b]
+        return out
+
+
 class Problem:
     """CORE/Problem.scala:16-33 — never owns cost / loss objects; keeps Python
     references so the GC cannot collect objects native code still points at."""
+
+    class EvaluateOptions:
+        """ceres::Problem::EvaluateOptions: which residual blocks (rows, in list order), which parameter blocks (columns, in list
+        order; a block left out is held constant) and whether the loss functions are applied.  Empty lists: all."""
+
+        def __init__(self):
+            self._h = lib().sk_evaluate_options_new()
+            self._arrays = []
+
+        def __del__(self):
+            if getattr(self, "_h", None) and _lib is not None:
+                _lib.sk_evaluate_options_free(self._h)
+                self._h = None
+
+        def setApplyLossFunction(self, on):
+            _check(lib().sk_evaluate_options_set_apply_loss_function(self._h, int(bool(on))))
+
+        def setResidualBlocks(self, ids):
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            _check(lib().sk_evaluate_options_set_residual_blocks(self._h, ids.ctypes.data_as(_ip), int(ids.size)))
+
+        def setParameterBlocks(self, blocks):
+            """blocks: DoubleArrays (or slices of one) that are parameter blocks of the problem."""
+            self._arrays = list(blocks)
+            pp = (_dp * max(len(self._arrays), 1))(*[b.cast() for b in self._arrays])
+            _check(lib().sk_evaluate_options_set_parameter_blocks(self._h, pp, len(self._arrays)))
+
+        def setDevice(self, device):
+            _check(lib().sk_evaluate_options_set_device(self._h, int(device)))
+
+        def setLaunchTiming(self, on):
+            _check(lib().sk_evaluate_options_set_launch_timing(self._h, int(bool(on))))
+
+        def launchSeconds(self):
+            """device seconds of the last evaluate's phases: uploads, evaluation, finish, gradient, cost, downloads"""
+            return [lib().sk_evaluate_options_launch_seconds(self._h, i) for i in range(6)]
 
     def __init__(self):
         self._h = lib().sk_problem_new()
@@ -1140,6 +1202,49 @@ class Problem:
                                               pob.ctypes.data_as(_ip))
         _check(rc)
         return cuts, nc.value, npts.value, pob
+
+    # ceres::Problem::Evaluate (ceres/problem.h via ceres.i)
+    def _evaluate_sizes(self, options):
+        rows, cols, nnz = C.c_int(), C.c_int(), C.c_longlong()
+        rc = lib().sk_problem_evaluate_sizes(self._h, options._h if options is not None else None, C.byref(rows), C.byref(cols), C.byref(nnz))
+        if rc == 1:
+            raise ValueError(lib().sk_last_error().decode())
+        _check(rc)
+        return rows.value, cols.value, nnz.value
+
+    def evaluateStructure(self, options=None):
+        """The CRSMatrix Problem.evaluate would fill, without its values: host logic, no device needed."""
+        num_rows, num_cols, nnz = self._evaluate_sizes(options)
+        rows, cols = np.zeros(num_rows + 1, dtype=np.int32), np.zeros(max(nnz, 1), dtype=np.int32)
+        _check(lib().sk_problem_evaluate_structure(self._h, options._h if options is not None else None, rows.ctypes.data_as(_ip), cols.ctypes.data_as(_ip)))
+        return CRSMatrix(num_rows, num_cols, rows, cols[:nnz])
+
+    def evaluate(self, options=None, cost=True, residuals=True, gradient=True, jacobian=True):
+        """Problem::Evaluate at the current contents of the parameter memory, on the device: a dict with what was asked for of
+        "cost" (float), "residuals", "gradient" (numpy arrays) and "jacobian" (CRSMatrix)."""
+        num_rows, num_cols, nnz = self._evaluate_sizes(options)
+        c = C.c_double()
+        r = np.zeros(max(num_rows, 1)) if residuals else None
+        g = np.zeros(max(num_cols, 1)) if gradient else None
+        v = np.zeros(max(nnz, 1)) if jacobian else None
+        rc = lib().sk_problem_evaluate(self._h, options._h if options is not None else None, C.byref(c) if cost else None,
+                                       r.ctypes.data_as(_dp) if residuals else None, g.ctypes.data_as(_dp) if gradient else None,
+                                       v.ctypes.data_as(_dp) if jacobian else None)
+        if rc == 1:
+            raise ValueError(lib().sk_last_error().decode())
+        _check(rc)
+        out = {}
+        if cost:
+            out["cost"] = c.value
+        if residuals:
+            out["residuals"] = r[:num_rows]
+        if gradient:
+            out["gradient"] = g[:num_cols]
+        if jacobian:
+            m = self.evaluateStructure(options)
+            m.values = v[:nnz]
+            out["jacobian"] = m
+        return out
 
     def numResidualBlocks(self):
         return lib().sk_problem_num_residual_blocks(self._h)

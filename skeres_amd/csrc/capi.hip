@@ -7,6 +7,8 @@
 #include "bal_kernels.hpp"
 #include "dense_kernels.hpp"
 #include "dense_rows_kernels.hpp"
+#include "evaluate_kernels.hpp"
+#include "evaluate_plan.hpp"
 #include "solver.hpp"
 
 using namespace sk;
@@ -19,6 +21,7 @@ struct sk_local_parameterization { LocalParameterization p; };
 struct sk_options { Options o; };
 struct sk_summary { Summary s; };
 struct sk_solver { std::unique_ptr<SolverBase> impl; };
+struct sk_evaluate_options { EvaluateOptions o; bool launch_timing = false; double launch_seconds[kEvaluatePhases] = {0, 0, 0, 0, 0, 0}; };
 
 static std::string g_program_name;
 
@@ -577,6 +580,70 @@ int sk_problem_num_residual_blocks(const sk_problem* p) { return (int)p->p.rb_fu
 int sk_problem_num_parameter_blocks(const sk_problem* p) { return (int)p->p.block_size.size(); }
 int sk_problem_num_parameters(const sk_problem* p) { return p->p.num_parameters(); }
 int sk_problem_num_residuals(const sk_problem* p) { return (int)p->p.num_residuals; }
+
+// ---- Problem::Evaluate (ceres/problem.h via ceres.i) ---------------------------------------
+sk_evaluate_options* sk_evaluate_options_new(void) { return new (std::nothrow) sk_evaluate_options(); }
+void sk_evaluate_options_free(sk_evaluate_options* o) { delete o; }
+int sk_evaluate_options_set_apply_loss_function(sk_evaluate_options* o, int on) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.apply_loss_function = on != 0; return SK_OK;
+}
+int sk_evaluate_options_set_residual_blocks(sk_evaluate_options* o, const sk_residual_block_id* ids, int n) {
+  SK_GUARD_BEGIN
+  if (!o || n < 0 || (n > 0 && !ids)) { set_error("sk_evaluate_options_set_residual_blocks: bad arguments"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.residual_blocks.assign(ids, ids + n);
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_evaluate_options_set_parameter_blocks(sk_evaluate_options* o, double* const* blocks, int n) {
+  SK_GUARD_BEGIN
+  if (!o || n < 0 || (n > 0 && !blocks)) { set_error("sk_evaluate_options_set_parameter_blocks: bad arguments"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.parameter_blocks.assign(blocks, blocks + n);
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_evaluate_options_set_device(sk_evaluate_options* o, int dev) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.device = dev; return SK_OK;
+}
+int sk_evaluate_options_set_launch_timing(sk_evaluate_options* o, int on) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  o->launch_timing = on != 0; return SK_OK;
+}
+double sk_evaluate_options_launch_seconds(const sk_evaluate_options* o, int phase) { return (o && phase >= 0 && phase < kEvaluatePhases) ? o->launch_seconds[phase] : NAN; }
+
+int sk_problem_evaluate_sizes(const sk_problem* p, const sk_evaluate_options* o, int* num_rows, int* num_cols, long long* num_nonzeros) {
+  SK_GUARD_BEGIN
+  if (!p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  EvaluatePlan plan;
+  std::string why;
+  const int rc = evaluate_plan_build(p->p, o ? &o->o : nullptr, false, false, false, &plan, &why);
+  if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
+  if (num_rows) *num_rows = plan.num_rows;
+  if (num_cols) *num_cols = plan.num_cols;
+  if (num_nonzeros) *num_nonzeros = plan.num_nonzeros;
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_problem_evaluate_structure(const sk_problem* p, const sk_evaluate_options* o, int* rows, int* cols) {
+  SK_GUARD_BEGIN
+  if (!p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  EvaluatePlan plan;
+  std::string why;
+  const int rc = evaluate_plan_build(p->p, o ? &o->o : nullptr, true, false, false, &plan, &why);
+  if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
+  if (rows) std::memcpy(rows, plan.rows.data(), plan.rows.size() * sizeof(int));
+  if (cols && !plan.cols.empty()) std::memcpy(cols, plan.cols.data(), plan.cols.size() * sizeof(int));
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_problem_evaluate(sk_problem* p, const sk_evaluate_options* o, double* cost, double* residuals, double* gradient, double* jacobian_values) {
+  SK_GUARD_BEGIN
+  if (!p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  double* seconds = o && o->launch_timing ? const_cast<sk_evaluate_options*>(o)->launch_seconds : nullptr;
+  return problem_evaluate(p->p, o ? &o->o : nullptr, cost, residuals, gradient, jacobian_values, seconds);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
 
 // ---- Options --------------------------------------------------------------------------
 sk_options* sk_options_new(void) { return new (std::nothrow) sk_options(); }

@@ -41,8 +41,11 @@ def main(argv):
     options.setLinearSolverType(sk.LinearSolverType.DENSE_SCHUR)
     options.setMinimizerProgressToStdout(True)
     summary = sk.Solver.Summary()
+    rms = lambda: (2.0 * problem.evaluate(residuals=False, gradient=False, jacobian=False)["cost"] / problem.numResiduals()) ** 0.5
+    print("Reprojection RMS before: %.6f px" % rms())
     sk.ceres.solve(options, problem, summary)
     print(summary.fullReport())
+    print("Reprojection RMS after: %.6f px" % rms())
     return 0
 
 
