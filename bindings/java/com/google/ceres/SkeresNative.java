@@ -121,6 +121,10 @@ public final class SkeresNative {
   public static native int skOptionsSetJacobiScaling(long o, int v);
   public static native int skOptionsSetMaxNumConsecutiveInvalidSteps(long o, int v);
   public static native int skOptionsSetDevice(long o, int v);
+  public static native int skOptionsSetPreconditionerType(long o, int v);
+  public static native int skOptionsSetEta(long o, double v);
+  public static native int skOptionsSetMaxLinearSolverIterations(long o, int v);
+  public static native int skOptionsSetMinLinearSolverIterations(long o, int v);
   public static native int skOptionsSetCholeskyEnvelope(long o, int v);
   public static native int skOptionsSetCholeskyDissection(long o, int v);
   public static native int skOptionsSetCholeskyBorder(long o, int v);

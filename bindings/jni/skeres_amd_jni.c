@@ -313,6 +313,10 @@ SK_OPT_DBL(skOptionsSetMaxLmDiagonal, sk_options_set_max_lm_diagonal)
 SK_OPT_INT(skOptionsSetJacobiScaling, sk_options_set_jacobi_scaling)
 SK_OPT_INT(skOptionsSetMaxNumConsecutiveInvalidSteps, sk_options_set_max_num_consecutive_invalid_steps)
 SK_OPT_INT(skOptionsSetDevice, sk_options_set_device)
+SK_OPT_INT(skOptionsSetPreconditionerType, sk_options_set_preconditioner_type)
+SK_OPT_DBL(skOptionsSetEta, sk_options_set_eta)
+SK_OPT_INT(skOptionsSetMaxLinearSolverIterations, sk_options_set_max_linear_solver_iterations)
+SK_OPT_INT(skOptionsSetMinLinearSolverIterations, sk_options_set_min_linear_solver_iterations)
 SK_OPT_INT(skOptionsSetCholeskyEnvelope, sk_options_set_cholesky_envelope)
 SK_OPT_INT(skOptionsSetCholeskyDissection, sk_options_set_cholesky_dissection)
 SK_OPT_INT(skOptionsSetCholeskyBorder, sk_options_set_cholesky_border)

@@ -49,8 +49,11 @@ typedef enum sk_linear_solver_type {
   SK_DENSE_SCHUR = 3,
   SK_SPARSE_SCHUR = 4,    /* not implemented */
   SK_ITERATIVE_SCHUR = 5, /* not implemented */
-  SK_CGNR = 6             /* not implemented */
+  SK_CGNR = 6             /* conjugate gradients on the normal equations over the block-sparse Jacobian */
 } sk_linear_solver_type;
+
+/* ceres::PreconditionerType, the two that CGNR takes */
+typedef enum sk_preconditioner_type { SK_IDENTITY = 0, SK_JACOBI = 1 } sk_preconditioner_type;
 
 /* ceres::MinimizerType; EX/Powell.scala:78 */
 typedef enum sk_minimizer_type { SK_LINE_SEARCH = 0, SK_TRUST_REGION = 1 } sk_minimizer_type;
@@ -396,6 +399,22 @@ int sk_options_set_min_lm_diagonal(sk_options* o, double v);
 int sk_options_set_max_lm_diagonal(sk_options* o, double v);
 int sk_options_set_jacobi_scaling(sk_options* o, int on);
 int sk_options_set_max_num_consecutive_invalid_steps(sk_options* o, int n);
+/* CGNR (linear solver type SK_CGNR): every trust-region step is an inexact Newton step — preconditioned conjugate gradients on
+ * (J^T J + D^2) y = -J^T r, the matrix applied as two products with the block-sparse Jacobian and never formed (Ceres 1.x's
+ * ConjugateGradientsSolver: stop when it * (Q_it - Q_it-1) / Q_it < eta and it >= min_linear_solver_iterations, or at
+ * max_linear_solver_iterations, whose step is used; the residual is formed anew as b - A x every tenth iteration).  Defaults:
+ * JACOBI (the block diagonal of the matrix over the parameter blocks), eta 0.1, at most 500 and at least 0 iterations.
+ * SK_ERR_INVALID_ARGUMENT: a preconditioner type other than the two, eta outside (0, 1), a negative count, min > max.
+ * Taken: device functors and recorded functors, robust losses, constant blocks, the four local parameterizations,
+ * bundle-adjustment-shaped problems (as the full camera + point system).  Refused with SK_ERR_UNSUPPORTED when the solver is
+ * created: host-evaluated (director) residual blocks, a parameter block of tangent size above 16, DOGLEG, parameter bounds, a
+ * world of more than one rank, dense-row problems.  sk_options_set_cholesky_tuning has no effect.  The iteration is enqueued
+ * launch by launch (sk_solver_stat "graph_replay" is 0); the step does not depend on how many CG iterations are enqueued
+ * between two reads of the device's done flag. */
+int sk_options_set_preconditioner_type(sk_options* o, int type);
+int sk_options_set_eta(sk_options* o, double eta);
+int sk_options_set_max_linear_solver_iterations(sk_options* o, int n);
+int sk_options_set_min_linear_solver_iterations(sk_options* o, int n);
 /* MI355X-side knobs (no reference counterpart) */
 int sk_options_set_device(sk_options* o, int hip_device);             /* default: current device */
 int sk_options_set_stream(sk_options* o, void* hip_stream);           /* default: a private stream */
@@ -547,12 +566,14 @@ const char* sk_summary_full_report(const sk_summary* s);     /* Summary.fullRepo
  * 0 cost, 1 cost_change, 2 gradient_max_norm, 3 step_norm, 4 relative_decrease,
  * 5 trust_region_radius, 6 step_is_valid, 7 step_is_successful,
  * 8 step_size (the line search's alpha under parameter bounds; 1 without), 9 line_search_evaluations (candidate costs
- * evaluated in the iteration: the ls_iter column; 1 without bounds) */
+ * evaluated in the iteration: the ls_iter column; 1 without bounds), 10 linear_solver_iterations (CGNR: the CG iterations of
+ * the iteration's linear solve; 0 for the factorisation solvers) */
 int sk_summary_num_logged_iterations(const sk_summary* s);
 double sk_summary_iteration_field(const sk_summary* s, int iteration, int field);
 /* Device time per phase, seconds, summed over the solve (HIP events on the
  * solver's stream). phase: 0 jacobian_eval, 1 schur_assemble (or J^T J),
- * 2 cholesky (or QR), 3 back_substitute, 4 cost_eval, 5 allreduce, 6 total */
+ * 2 cholesky (or QR), 3 back_substitute, 4 cost_eval, 5 allreduce, 6 total.
+ * CGNR: 1 the block sums and the preconditioner, 2 the CG loop, 3 the model and the candidate */
 double sk_summary_phase_seconds(const sk_summary* s, int phase);
 /* Summary.linear_solver_type_used / _given (ceres::Solver::Summary; SWIG exposes both through /root/reference ceres.i:186-210).
    They differ when DENSE_SCHUR was asked for on a problem without the 2-residual / 9- and 3-parameter block structure: the
@@ -622,6 +643,10 @@ int sk_solver_distribution(const sk_solver* s, double* allreduce_seconds, double
  *   "bounded_coordinates"   coordinates with a finite bound (sk_problem_set_parameter_lower_bound / _upper_bound)
  *   "active_bounds"         coordinates of the current x that sit exactly on a bound
  *   "line_search_evaluations" candidate costs evaluated by the line search under bounds, since the solver was created
+ * CGNR:
+ *   "cg_iterations" CG iterations since the solver was created, "cg_iterations_last" of the last linear solve,
+ *   "cg_status_last" how it ended (0 the stopping test, 1 the iteration limit, 2 breakdown, 3 zero right-hand side; -1 before
+ *   the first), "cg_batches" reads of the done flag, "jacobian_nonzeros" stored entries of the block-sparse Jacobian
  * dense rows (DENSE_NORMAL_CHOLESKY over one parameter block):
  *   "jtj_flops_algorithmic" m n (n + 1): SURVEY.md section 8(d)'s figure for J^T J (sk_solver_syrk_flops_per_solve counts
  *                           the padded 128 x 128 tiles the launch computes) */

@@ -24,7 +24,7 @@ from .api import (  # noqa: F401
     SnavelyReprojectionError, ExponentialResidual, PowellF1, PowellF2, PowellF3, PowellF4,
     BinaryScalarCost, BinaryVector3Cost, TenParameterCost, HelloCostFunctor, QuaternionRotationError,
     LocalParameterization, PredefinedLocalParameterizations,
-    PredefinedLossFunctions, LossFunction, Problem, CRSMatrix, Solver, LinearSolverType, MinimizerType, TrustRegionStrategyType, DoglegType, TerminationType,
+    PredefinedLossFunctions, LossFunction, Problem, CRSMatrix, Solver, LinearSolverType, PreconditionerType, MinimizerType, TrustRegionStrategyType, DoglegType, TerminationType,
     ceres, StepSolver,
 )
 from . import bal  # noqa: F401

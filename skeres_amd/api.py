@@ -115,6 +115,10 @@ _SIGS = {
     "sk_options_set_jacobi_scaling": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_options_set_max_num_consecutive_invalid_steps": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_options_set_device": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_options_set_preconditioner_type": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_options_set_eta": (C.c_int, [C.c_void_p, C.c_double]),
+    "sk_options_set_max_linear_solver_iterations": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_options_set_min_linear_solver_iterations": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_options_set_cholesky_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "sk_options_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sk_options_set_distributed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ALLREDUCE_FN, C.c_void_p]),
@@ -965,6 +969,10 @@ class LinearSolverType:
     DENSE_NORMAL_CHOLESKY, DENSE_QR, SPARSE_NORMAL_CHOLESKY, DENSE_SCHUR, SPARSE_SCHUR, ITERATIVE_SCHUR, CGNR = range(7)
 
 
+class PreconditionerType:  # ceres::PreconditionerType, the two that CGNR takes
+    IDENTITY, JACOBI = 0, 1
+
+
 class MinimizerType:
     LINE_SEARCH, TRUST_REGION = 0, 1
 
@@ -1296,6 +1304,11 @@ class Solver:
         def setJacobiScaling(self, on): self._set("jacobi_scaling", int(bool(on)))
         def setMaxNumConsecutiveInvalidSteps(self, n): self._set("max_num_consecutive_invalid_steps", int(n))
         def setDevice(self, d): self._set("device", int(d))
+        # CGNR (include/skeres_amd.h)
+        def setPreconditionerType(self, t): self._set("preconditioner_type", int(t))
+        def setEta(self, v): self._set("eta", float(v))
+        def setMaxLinearSolverIterations(self, n): self._set("max_linear_solver_iterations", int(n))
+        def setMinLinearSolverIterations(self, n): self._set("min_linear_solver_iterations", int(n))
 
         def setCholeskyTuning(self, group=0, lookahead=True):
             _check(lib().sk_options_set_cholesky_tuning(self._h, int(group), int(bool(lookahead))))
@@ -1384,7 +1397,8 @@ class Solver:
 
         def iterations(self):
             names = ["cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease",
-                     "trust_region_radius", "step_is_valid", "step_is_successful", "step_size", "line_search_evaluations"]
+                     "trust_region_radius", "step_is_valid", "step_is_successful", "step_size", "line_search_evaluations",
+                     "linear_solver_iterations"]
             return [{nm: lib().sk_summary_iteration_field(self._h, i, k) for k, nm in enumerate(names)}
                     for i in range(lib().sk_summary_num_logged_iterations(self._h))]
 

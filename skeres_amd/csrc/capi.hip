@@ -8,6 +8,7 @@
 #include "dense_kernels.hpp"
 #include "dense_rows_kernels.hpp"
 #include "evaluate_kernels.hpp"
+#include "cgnr_plan.hpp"
 #include "evaluate_plan.hpp"
 #include "solver.hpp"
 
@@ -76,6 +77,7 @@ const DevKnobs& dev_knobs() {
     k.pair_max_trailing = num("SK_CHAIN_PAIR_MAX_TRAILING", 0);
     k.dissect_at = num("SK_DISSECT_AT", -1);
     k.schedule_plain = num("SK_SCHEDULE_PLAIN", 0);
+    k.cgnr_batch = num("SK_CGNR_BATCH", 0);
     k.chain_xcd_local = num("SK_CHAIN_XCD_LOCAL", 0);
     if (const char* e = getenv("SK_BS_PAIR")) k.bs_pair = atoi(e);
     if (const char* e = getenv("SK_BS_SPREAD")) k.bs_spread = atoi(e);
@@ -649,7 +651,7 @@ int sk_problem_evaluate(sk_problem* p, const sk_evaluate_options* o, double* cos
 sk_options* sk_options_new(void) { return new (std::nothrow) sk_options(); }
 void sk_options_free(sk_options* o) { delete o; }
 int sk_options_set_linear_solver_type(sk_options* o, int t) {
-  if (t != SK_DENSE_NORMAL_CHOLESKY && t != SK_DENSE_QR && t != SK_DENSE_SCHUR) { set_error("linear solver type %s is not implemented (DENSE_QR, DENSE_NORMAL_CHOLESKY, DENSE_SCHUR are)", linear_solver_name(t)); return SK_ERR_UNSUPPORTED; }
+  if (t != SK_DENSE_NORMAL_CHOLESKY && t != SK_DENSE_QR && t != SK_DENSE_SCHUR && t != SK_CGNR) { set_error("linear solver type %s is not implemented (DENSE_QR, DENSE_NORMAL_CHOLESKY, DENSE_SCHUR, CGNR are)", linear_solver_name(t)); return SK_ERR_UNSUPPORTED; }
   o->o.linear_solver_type = t; return SK_OK;
 }
 int sk_options_set_minimizer_type(sk_options* o, int t) {
@@ -680,6 +682,22 @@ SK_SET_D(min_lm_diagonal, min_lm_diagonal)
 SK_SET_D(max_lm_diagonal, max_lm_diagonal)
 int sk_options_set_jacobi_scaling(sk_options* o, int on) { o->o.jacobi_scaling = on != 0; return SK_OK; }
 int sk_options_set_max_num_consecutive_invalid_steps(sk_options* o, int n) { if (n < 1) { set_error("must be >= 1"); return SK_ERR_INVALID_ARGUMENT; } o->o.max_num_consecutive_invalid_steps = n; return SK_OK; }
+int sk_options_set_preconditioner_type(sk_options* o, int t) {
+  if (t != SK_IDENTITY && t != SK_JACOBI) { set_error("invalid preconditioner type %d (IDENTITY and JACOBI are implemented)", t); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.preconditioner_type = t; return SK_OK;
+}
+int sk_options_set_eta(sk_options* o, double v) {
+  if (!(v > 0.0 && v < 1.0)) { set_error("eta must lie inside (0, 1)"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.eta = v; return SK_OK;
+}
+int sk_options_set_max_linear_solver_iterations(sk_options* o, int n) {
+  if (n < 0 || n < o->o.min_linear_solver_iterations) { set_error("max_linear_solver_iterations must be >= 0 and >= min_linear_solver_iterations (%d)", o->o.min_linear_solver_iterations); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.max_linear_solver_iterations = n; return SK_OK;
+}
+int sk_options_set_min_linear_solver_iterations(sk_options* o, int n) {
+  if (n < 0 || n > o->o.max_linear_solver_iterations) { set_error("min_linear_solver_iterations must be >= 0 and <= max_linear_solver_iterations (%d)", o->o.max_linear_solver_iterations); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.min_linear_solver_iterations = n; return SK_OK;
+}
 int sk_options_set_device(sk_options* o, int dev) { o->o.device = dev; return SK_OK; }
 int sk_options_set_cholesky_tuning(sk_options* o, int group, int lookahead) {
   if (group > 64) { set_error("group must be <= 64"); return SK_ERR_INVALID_ARGUMENT; }
@@ -760,7 +778,7 @@ double sk_summary_iteration_field(const sk_summary* s, int it, int field) {
   switch (field) {
     case 0: return L.cost; case 1: return L.cost_change; case 2: return L.gradient_max_norm; case 3: return L.step_norm;
     case 4: return L.relative_decrease; case 5: return L.trust_region_radius; case 6: return L.step_is_valid; case 7: return L.step_is_successful;
-    case 8: return L.step_size; case 9: return L.line_search_evaluations;
+    case 8: return L.step_size; case 9: return L.line_search_evaluations; case 10: return L.linear_solver_iterations;
   }
   return NAN;
 }
@@ -774,6 +792,11 @@ static std::unique_ptr<SolverBase> make_solver(const Options& o, Problem* p, int
   if (p->has_parameterization() && o.linear_solver_type != SK_DENSE_SCHUR && problem_is_dense_rows(*p)) {
     set_error("local parameterizations and constant parameter blocks are implemented for residual-block problems (DENSE_QR / DENSE_NORMAL_CHOLESKY; identity, subset and constant blocks under DENSE_SCHUR), not for dense rows (not supported here)");
     *rc = SK_ERR_UNSUPPORTED; return nullptr;
+  }
+  if (o.linear_solver_type == SK_CGNR) {  // every shape it takes, bundle adjustment included, as the full system: no elimination
+    const std::string refusal = cgnr_refusal(*p, o.world, o.trust_region_strategy_type == SK_DOGLEG);  // (host data alone: before any device is touched)
+    if (!refusal.empty()) { set_error("%s", refusal.c_str()); *rc = SK_ERR_UNSUPPORTED; return nullptr; }
+    return make_cgnr_solver(o, p);
   }
   if (o.linear_solver_type == SK_DENSE_SCHUR) {
     std::string why;

@@ -75,6 +75,10 @@ struct Options {  // Solver.Options; Ceres 1.x defaults
   double min_relative_decrease = 1e-3, min_lm_diagonal = 1e-6, max_lm_diagonal = 1e32;
   bool jacobi_scaling = true;
   int max_num_consecutive_invalid_steps = 5;
+  // CGNR (common.hpp: namespace cgnr): the preconditioner, the forcing sequence's eta, the bounds on the CG iterations of one linear solve
+  int preconditioner_type = SK_JACOBI;
+  double eta = 0.1;
+  int max_linear_solver_iterations = 500, min_linear_solver_iterations = 0;
   int device = -1;
   hipStream_t stream = nullptr;
   bool stream_set = false;
@@ -126,6 +130,16 @@ constexpr double kMinStepSize = 1e-9;                                     // of 
 constexpr double kBisection = 0.5;                                        // after a trial whose cost is not finite
 }  // namespace bounds
 
+// CGNR: Ceres 1.x's ConjugateGradientsSolver on the damped normal equations, applied as two products with the block-sparse
+// Jacobian; recalled, not pinned (like SURVEY.md §8a row a13), so the constants live here and nowhere else.
+namespace cgnr {
+constexpr int kResidualResetPeriod = 10;  // res = b - A x instead of res -= alpha q when it % 10 == 0
+constexpr int kBatch = 8;                 // CG iterations enqueued between two reads of the done flag (SK_CGNR_BATCH)
+constexpr int kPartSlots = 64;            // a column block's slot list is summed in parts of this many slots (cgnr_plan.hpp)
+// how a linear solve ended ("cg_status_last" of sk_solver_stat); kRunning on the device only
+enum Status { kConverged = 0, kIterationLimit = 1, kBreakdown = 2, kZeroRhs = 3, kRunning = -1 };
+}  // namespace cgnr
+
 struct IterationLog {
   int iteration = 0;
   double cost = 0, cost_change = 0, gradient_max_norm = 0, step_norm = 0, relative_decrease = 0,
@@ -133,6 +147,7 @@ struct IterationLog {
   int step_is_valid = 1, step_is_successful = 1;
   double step_size = 1.0;           // the line search's alpha under parameter bounds
   int line_search_evaluations = 1;  // candidate costs evaluated in the iteration
+  int linear_solver_iterations = 0; // CGNR: CG iterations of the iteration's linear solve (0 for the factorisation solvers)
 };
 
 struct Summary {
@@ -150,6 +165,8 @@ struct Summary {
   int num_e_blocks = 0, num_f_blocks = 0;
   int world = 1;
   int trust_region_strategy_type = SK_LEVENBERG_MARQUARDT;
+  int preconditioner_type = SK_JACOBI;  // CGNR
+  long linear_solver_iterations = 0;    // CGNR: total over the solve
   std::string device_name;
   std::string brief, full;
   void build_reports();

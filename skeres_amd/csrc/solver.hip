@@ -158,6 +158,7 @@ void SolverBase::log_iteration(int it, double cost_change, double step_norm, dou
   L.step_norm = step_norm; L.relative_decrease = rho; L.trust_region_radius = radius_;
   L.step_is_valid = valid; L.step_is_successful = success; L.iter_time = iter_time; L.total_time = now();
   L.step_size = ls_alpha_; L.line_search_evaluations = ls_evals_;
+  L.linear_solver_iterations = it == 0 ? 0 : cg_iterations_last_;
   sum_.iterations.push_back(L);
   if (opt_.progress_to_stdout && opt_.rank == 0) {
     if (it == 0) printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius  ls_iter  iter_time  total_time\n");
@@ -324,7 +325,7 @@ int SolverBase::step(bool* done) {
   }
   const double t_iter = now();
   ++iteration_;
-  ls_alpha_ = 1.0; ls_evals_ = 1;
+  ls_alpha_ = 1.0; ls_evals_ = 1; cg_iterations_last_ = 0;
   bool valid = false;
   double mcc = 0.0, new_cost = 0.0, step_norm = 0.0;
   int rc = try_step(radius_, &valid, &mcc, &new_cost, &step_norm);
@@ -431,6 +432,10 @@ void Summary::build_reports() {
     // (Ceres reports "Given / Used"; its alternate for a Schur-type solver with nothing to eliminate is DENSE_QR too)
     snprintf(b, sizeof(b), "Linear solver given    %22s   (no 2-residual / 9- and 3-parameter block structure to eliminate: its alternate is used)\n",
              linear_solver_name(linear_solver_type_given));
+    f += b;
+  }
+  if (linear_solver_type == SK_CGNR) {
+    snprintf(b, sizeof(b), "Preconditioner         %22s\nLinear solver iterations    % 12ld\n", preconditioner_type == SK_JACOBI ? "JACOBI" : "IDENTITY", linear_solver_iterations);
     f += b;
   }
   if (linear_solver_type == SK_DENSE_SCHUR) {

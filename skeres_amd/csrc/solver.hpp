@@ -97,6 +97,7 @@ class SolverBase {
   int check_bounds();  // create(): the refusals, the feasibility of the box
   bool bounded_ = false, infeasible_ = false;
   double ls_alpha_ = 1.0;          // of the last iteration
+  int cg_iterations_last_ = 0;     // CGNR: CG iterations of the iteration's linear solve (the log's linear_solver_iterations)
   int ls_evals_ = 1;
   long n_ls_evals_ = 0;            // since create ("line_search_evaluations")
   long bounded_coordinates_ = 0, active_bounds_ = 0;
@@ -150,5 +151,7 @@ std::unique_ptr<SolverBase> make_dense_solver(const Options& o, Problem* p);
 // Tall dense rows over one parameter block (transposed Jacobian + long-K MFMA SYRK): DENSE_NORMAL_CHOLESKY.
 std::unique_ptr<SolverBase> make_dense_rows_solver(const Options& o, Problem* p);
 bool problem_is_dense_rows(const Problem& p);
+// Block-sparse Jacobian, never J^T J: CGNR (preconditioned conjugate gradients on the damped normal equations as two products).
+std::unique_ptr<SolverBase> make_cgnr_solver(const Options& o, Problem* p);
 
 }  // namespace sk
