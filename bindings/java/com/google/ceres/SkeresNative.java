@@ -98,6 +98,21 @@ public final class SkeresNative {
   public static native int skProblemEvaluateSizes(long p, long o, long[] sizes);
   public static native int skProblemEvaluateStructure(long p, long o, int[] rows, int[] cols);
   public static native int skProblemEvaluate(long p, long o, double[] cost, double[] residuals, double[] gradient, double[] values);
+  // ceres::Covariance / Covariance::Options (ceres/covariance.h via ceres.i:29,141); options may be 0 (defaults); blocks are native addresses.
+  // compute returns 0, or 5 where the Jacobian is rank deficient (no exception: Covariance.compute answers false); every other failure throws
+  public static native long skCovarianceOptionsNew();
+  public static native void skCovarianceOptionsFree(long o);
+  public static native int skCovarianceOptionsSetApplyLossFunction(long o, int on);
+  public static native int skCovarianceOptionsSetMinReciprocalConditionNumber(long o, double v);
+  public static native int skCovarianceOptionsSetDevice(long o, int device);
+  public static native long skCovarianceNew(long o);
+  public static native void skCovarianceFree(long c);
+  public static native int skCovarianceCompute(long c, long p, long[] blocks1, long[] blocks2);
+  public static native int skCovarianceComputeBlocks(long c, long p, long[] blocks);
+  public static native int skCovarianceBlockSizes(long c, long block, int[] sizes);
+  public static native int skCovarianceGetBlock(long c, long b1, long b2, int tangent, double[] out);
+  public static native int skCovarianceGetMatrix(long c, long[] blocks, int tangent, double[] out);
+  public static native double skCovarianceStat(long c, String name);
   // Solver.Options
   public static native long skOptionsNew();
   public static native void skOptionsFree(long o);

@@ -445,3 +445,89 @@ SK_JNI(jint, skProblemEvaluate)(JNIEnv* env, jclass c, jlong p, jlong o, jdouble
   if ((*env)->ExceptionCheck(env)) return (jint)rc;  /* an evaluate() upcall threw: let that exception propagate */
   return check(env, rc);
 }
+
+/* ---- Covariance (ceres/covariance.h via ceres.i:29,141): Covariance and Covariance.Options in Native.scala ---------------------- */
+SK_JNI(jlong, skCovarianceOptionsNew)(JNIEnv* env, jclass c) { (void)c; return check_handle(env, sk_covariance_options_new()); }
+SK_JNI(void, skCovarianceOptionsFree)(JNIEnv* env, jclass c, jlong o) { (void)env; (void)c; sk_covariance_options_free(PTR(sk_covariance_options, o)); }
+SK_JNI(jint, skCovarianceOptionsSetApplyLossFunction)(JNIEnv* env, jclass c, jlong o, jint on) { (void)c; return check(env, sk_covariance_options_set_apply_loss_function(PTR(sk_covariance_options, o), on)); }
+SK_JNI(jint, skCovarianceOptionsSetMinReciprocalConditionNumber)(JNIEnv* env, jclass c, jlong o, jdouble v) { (void)c; return check(env, sk_covariance_options_set_min_reciprocal_condition_number(PTR(sk_covariance_options, o), v)); }
+SK_JNI(jint, skCovarianceOptionsSetDevice)(JNIEnv* env, jclass c, jlong o, jint device) { (void)c; return check(env, sk_covariance_options_set_device(PTR(sk_covariance_options, o), device)); }
+SK_JNI(jlong, skCovarianceNew)(JNIEnv* env, jclass c, jlong o) { (void)c; return check_handle(env, sk_covariance_new(PTR(sk_covariance_options, o))); }
+SK_JNI(void, skCovarianceFree)(JNIEnv* env, jclass c, jlong v) { (void)env; (void)c; sk_covariance_free(PTR(sk_covariance, v)); }
+/* the native addresses of n parameter blocks as a double*[] (NULL: out of memory) */
+static double** block_pointers(JNIEnv* env, jlongArray blocks, jsize* n) {
+  *n = (*env)->GetArrayLength(env, blocks);
+  double** ptrs = (double**)malloc(sizeof(double*) * (size_t)(*n ? *n : 1));
+  if (!ptrs) return NULL;
+  jlong* p = (*env)->GetLongArrayElements(env, blocks, NULL);
+  for (jsize i = 0; i < *n; ++i) ptrs[i] = PTR(double, p[i]);
+  (*env)->ReleaseLongArrayElements(env, blocks, p, JNI_ABORT);
+  return ptrs;
+}
+/* a rank-deficient Jacobian is an answer, not an exception (Covariance.compute returns false): the status comes back as it is */
+static jint check_compute(JNIEnv* env, int rc) {
+  if ((*env)->ExceptionCheck(env)) return (jint)rc;  /* an evaluate() upcall threw: let that exception propagate */
+  if (rc == SK_ERR_EVALUATION_FAILED && strstr(sk_last_error(), "rank deficient")) return (jint)rc;
+  return check(env, rc);
+}
+/* Director upcalls (host-callback blocks) arrive on this thread. */
+SK_JNI(jint, skCovarianceCompute)(JNIEnv* env, jclass c, jlong v, jlong p, jlongArray blocks1, jlongArray blocks2) {
+  (void)c;
+  jsize n1 = 0, n2 = 0;
+  double** b1 = block_pointers(env, blocks1, &n1);
+  double** b2 = block_pointers(env, blocks2, &n2);
+  int rc = SK_ERR_INVALID_ARGUMENT;
+  if (b1 && b2 && n1 == n2) rc = sk_covariance_compute(PTR(sk_covariance, v), PTR(sk_problem, p), b1, b2, (int)n1);
+  free(b2); free(b1);
+  return check_compute(env, rc);
+}
+SK_JNI(jint, skCovarianceComputeBlocks)(JNIEnv* env, jclass c, jlong v, jlong p, jlongArray blocks) {
+  (void)c;
+  jsize n = 0;
+  double** b = block_pointers(env, blocks, &n);
+  const int rc = b ? sk_covariance_compute_blocks(PTR(sk_covariance, v), PTR(sk_problem, p), b, (int)n) : SK_ERR_INVALID_ARGUMENT;
+  free(b);
+  return check_compute(env, rc);
+}
+/* sizes: int[2] = (size, tangent size) of a parameter block */
+SK_JNI(jint, skCovarianceBlockSizes)(JNIEnv* env, jclass c, jlong v, jlong block, jintArray sizes) {
+  (void)c;
+  int size = 0, tangent = 0;
+  const int rc = sk_covariance_block_sizes(PTR(sk_covariance, v), PTR(double, block), &size, &tangent);
+  if (rc == SK_OK) {
+    jint* s = (*env)->GetIntArrayElements(env, sizes, NULL);
+    s[0] = size; s[1] = tangent;
+    (*env)->ReleaseIntArrayElements(env, sizes, s, 0);
+  }
+  return check(env, rc);
+}
+SK_JNI(jint, skCovarianceGetBlock)(JNIEnv* env, jclass c, jlong v, jlong b1, jlong b2, jint tangent, jdoubleArray out) {
+  (void)c;
+  jdouble* po = (*env)->GetDoubleArrayElements(env, out, NULL);
+  const int rc = tangent ? sk_covariance_get_block_in_tangent_space(PTR(sk_covariance, v), PTR(double, b1), PTR(double, b2), po)
+                         : sk_covariance_get_block(PTR(sk_covariance, v), PTR(double, b1), PTR(double, b2), po);
+  (*env)->ReleaseDoubleArrayElements(env, out, po, rc == SK_OK ? 0 : JNI_ABORT);
+  return check(env, rc);
+}
+SK_JNI(jint, skCovarianceGetMatrix)(JNIEnv* env, jclass c, jlong v, jlongArray blocks, jint tangent, jdoubleArray out) {
+  (void)c;
+  jsize n = 0;
+  double** b = block_pointers(env, blocks, &n);
+  int rc = SK_ERR_INVALID_ARGUMENT;
+  if (b) {
+    jdouble* po = (*env)->GetDoubleArrayElements(env, out, NULL);
+    rc = tangent ? sk_covariance_get_matrix_in_tangent_space(PTR(sk_covariance, v), b, (int)n, po) : sk_covariance_get_matrix(PTR(sk_covariance, v), b, (int)n, po);
+    (*env)->ReleaseDoubleArrayElements(env, out, po, rc == SK_OK ? 0 : JNI_ABORT);
+  }
+  free(b);
+  return check(env, rc);
+}
+SK_JNI(jdouble, skCovarianceStat)(JNIEnv* env, jclass c, jlong v, jstring name) {
+  (void)c;
+  const char* nm = (*env)->GetStringUTFChars(env, name, NULL);
+  double value = 0.0;
+  const int rc = sk_covariance_stat(PTR(sk_covariance, v), nm, &value);
+  (*env)->ReleaseStringUTFChars(env, name, nm);
+  check(env, rc);
+  return value;
+}

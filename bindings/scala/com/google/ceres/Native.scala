@@ -197,6 +197,52 @@ object CeresProblem {
   class Options { def setCostFunctionOwnership(o: Ownership.Value): Unit = (); def setLossFunctionOwnership(o: Ownership.Value): Unit = () }
 }
 
+/** ceres::Covariance (ceres/covariance.h via ceres.i:29,141): blocks of (J^T J)^-1 at the current contents of the parameter memory, by the
+  * Cholesky factorisation of the scaled normal matrix on the device.  compute answers false where the Jacobian is rank deficient (there
+  * is no pseudo-inverse); the getters return row-major arrays, size(a) x size(b) or, in the tangent space, tangent(a) x tangent(b). */
+class Covariance(options: Covariance.Options) {
+  val handle: Long = SkeresNative.skCovarianceNew(if (options == null) 0L else options.handle)
+  /** Covariance::Compute(covariance_blocks, problem) */
+  def compute(covarianceBlocks: Seq[(DoublePointer, DoublePointer)], problem: CeresProblem): Boolean =
+    SkeresNative.skCovarianceCompute(handle, problem.handle, covarianceBlocks.map(_._1.address).toArray, covarianceBlocks.map(_._2.address).toArray) == 0
+  /** Covariance::Compute(parameter_blocks, problem): every pair among the blocks */
+  def computeBlocks(parameterBlocks: Seq[DoublePointer], problem: CeresProblem): Boolean =
+    SkeresNative.skCovarianceComputeBlocks(handle, problem.handle, parameterBlocks.map(_.address).toArray) == 0
+  private def sizeOf(block: DoublePointer, tangent: Boolean): Int = {
+    val sizes = new Array[Int](2)
+    SkeresNative.skCovarianceBlockSizes(handle, block.address, sizes)
+    if (tangent) sizes(1) else sizes(0)
+  }
+  private def block(a: DoublePointer, b: DoublePointer, tangent: Boolean): Array[Double] = {
+    val out = new Array[Double](math.max(1, sizeOf(a, tangent) * sizeOf(b, tangent)))
+    SkeresNative.skCovarianceGetBlock(handle, a.address, b.address, if (tangent) 1 else 0, out)
+    out
+  }
+  private def matrix(blocks: Seq[DoublePointer], tangent: Boolean): Array[Double] = {
+    val dim = blocks.map(sizeOf(_, tangent)).sum
+    val out = new Array[Double](math.max(1, dim * dim))
+    SkeresNative.skCovarianceGetMatrix(handle, blocks.map(_.address).toArray, if (tangent) 1 else 0, out)
+    out
+  }
+  def getCovarianceBlock(a: DoublePointer, b: DoublePointer): Array[Double] = block(a, b, false)
+  def getCovarianceBlockInTangentSpace(a: DoublePointer, b: DoublePointer): Array[Double] = block(a, b, true)
+  def getCovarianceMatrix(blocks: Seq[DoublePointer]): Array[Double] = matrix(blocks, false)
+  def getCovarianceMatrixInTangentSpace(blocks: Seq[DoublePointer]): Array[Double] = matrix(blocks, true)
+  /** "columns", "selected_columns", "normal_matrix_pairs", "reciprocal_pivot_ratio", "phase_seconds_0".."phase_seconds_4" of the last compute */
+  def stat(name: String): Double = SkeresNative.skCovarianceStat(handle, name)
+  override def finalize(): Unit = SkeresNative.skCovarianceFree(handle)
+}
+object Covariance {
+  /** ceres::Covariance::Options; algorithm_type, null_space_rank and num_threads have no counterpart. */
+  class Options {
+    val handle: Long = SkeresNative.skCovarianceOptionsNew()
+    def setApplyLossFunction(on: Boolean): Unit = SkeresNative.skCovarianceOptionsSetApplyLossFunction(handle, if (on) 1 else 0)
+    def setMinReciprocalConditionNumber(v: Double): Unit = SkeresNative.skCovarianceOptionsSetMinReciprocalConditionNumber(handle, v)
+    def setDevice(device: Int): Unit = SkeresNative.skCovarianceOptionsSetDevice(handle, device)
+    override def finalize(): Unit = SkeresNative.skCovarianceOptionsFree(handle)
+  }
+}
+
 object Solver {
   class Options {
     val handle: Long = SkeresNative.skOptionsNew()

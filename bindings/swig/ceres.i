@@ -53,6 +53,8 @@ void initGoogleLogging(const char* name) { sk_init_logging(name); }
 // (sk_problem_set_parameter_lower_bound / _upper_bound and their getters too, as the reference's come through ceres/problem.h, ceres.i:150)
 // (sk_evaluate_options_* and sk_problem_evaluate / _sizes / _structure too: ceres::Problem::Evaluate and ceres::CRSMatrix, which the reference's
 // ceres.i %include's with ceres/problem.h and ceres/crs_matrix.h; CeresProblem.evaluate in Native.scala binds them by hand over Java arrays)
+// (sk_covariance_options_* and sk_covariance_* too: ceres::Covariance and ceres::Covariance::Options, which the reference's ceres.i #include's and
+// %include's with ceres/covariance.h, ceres.i:29,141; Covariance in Native.scala binds them by hand over Java arrays)
 %include "skeres_amd.h"
 
 // load the native libraries as the reference's module class does (ceres.i:213-223)

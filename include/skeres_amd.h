@@ -381,6 +381,55 @@ int sk_problem_evaluate_structure(const sk_problem* p, const sk_evaluate_options
 int sk_problem_evaluate(sk_problem* p, const sk_evaluate_options* o, double* cost, double* residuals /* num_rows */,
                         double* gradient /* num_cols */, double* jacobian_values /* num_nonzeros */);
 
+/* ---- Covariance: ceres::Covariance and ceres::Covariance::Options ------------------------------------------------------------
+ * ceres/covariance.h, #include'd at ceres.i:29 and %include'd at ceres.i:141: both are classes of the JVM module that bindings/
+ * replaces.  The semantics are Ceres 1.x's, restated from memory like the rest:
+ *   C = (J^T J)^-1 with J the Jacobian sk_problem_evaluate would return at the CURRENT contents of the caller's parameter memory,
+ *   over all residual blocks and all parameter blocks, in the tangent space, loss-corrected iff apply_loss_function.
+ *   sizes      a block (a, b) is served in the tangent space, tangent(a) x tangent(b), or lifted to the ambient space,
+ *              P_a C_ab P_b^T, size(a) x size(b), with P = dPlus/ddelta at the current x (subset: zero rows and columns at the held
+ *              coordinates; quaternion: 4 x 4 of rank 3); both row-major;
+ *   constant   a constant block has covariance zero with everything, itself included; its tangent size is Problem::Evaluate's
+ *              (the local size of its parameterization, else its size);
+ *   algorithm  the Cholesky factorisation of the diagonally scaled normal matrix D J^T J D, dense, on the device (the conditioning
+ *              caveat of the normal equations applies: kappa(J^T J) = kappa(J)^2).  A rank-deficient Jacobian makes compute FAIL:
+ *              Ceres' DENSE_SVD pseudo-inverse, null_space_rank and algorithm_type have no counterpart.  Rank deficiency is decided
+ *              by (1) a diagonal entry of J^T J that is exactly 0 (a coordinate no residual depends on, a block in no residual
+ *              block) and (2) a pivot that is not positive, or min_j L_jj^2 / max_j L_jj^2 < min_reciprocal_condition_number;
+ *   pairs      (a, b) and (b, a) are one pair; duplicates are accepted and computed once; the getters answer both orders:
+ *              block(b, a) is block(a, b) transposed, bit for bit.
+ * Errors: SK_ERR_INVALID_ARGUMENT — a pointer that is no parameter block of the problem, num_pairs <= 0, a getter before a
+ * successful compute or for a pair that was not computed (get_matrix: any pair among the listed blocks); SK_ERR_NO_DEVICE —
+ * compute without a GPU (options, getters and validation need none); SK_ERR_EVALUATION_FAILED — a functor reported failure, or
+ * the Jacobian is rank deficient (sk_last_error names the first offending block and coordinate, else the pivot ratio; getters
+ * afterwards are SK_ERR_INVALID_ARGUMENT); SK_ERR_UNSUPPORTED — dense-row problems, a tangent size above 16, more than 32 768
+ * columns (the dense matrix of (N + k, padded to blocks of 128)^2 doubles is a cap on memory; covariance at bundle-adjustment scale
+ * through the reduced camera system is not built).  Host-callback blocks are taken; one device, no world of ranks. */
+typedef struct sk_covariance_options sk_covariance_options;   /* ceres::Covariance::Options (ceres/covariance.h via ceres.i:29,141) */
+typedef struct sk_covariance sk_covariance;                   /* ceres::Covariance (ceres/covariance.h via ceres.i:29,141) */
+sk_covariance_options* sk_covariance_options_new(void);       /* apply_loss_function 1, min_reciprocal_condition_number 1e-14, current device */
+void sk_covariance_options_free(sk_covariance_options* o);
+int sk_covariance_options_set_apply_loss_function(sk_covariance_options* o, int on);                  /* Covariance::Options::apply_loss_function */
+int sk_covariance_options_set_min_reciprocal_condition_number(sk_covariance_options* o, double v);    /* Covariance::Options::min_reciprocal_condition_number; [0, 1), not NaN */
+int sk_covariance_options_set_device(sk_covariance_options* o, int hip_device);                       /* (no reference counterpart) */
+sk_covariance* sk_covariance_new(const sk_covariance_options* o /* may be NULL */);                   /* Covariance::Covariance(options) */
+void sk_covariance_free(sk_covariance* c);
+/* Covariance::Compute(covariance_blocks, problem): the pairs (blocks1[i], blocks2[i]) */
+int sk_covariance_compute(sk_covariance* c, sk_problem* p, double* const* blocks1, double* const* blocks2, int num_pairs);
+/* Covariance::Compute(parameter_blocks, problem): every pair among the n blocks — the form a StdVectorDoublePointer (ceres.i:82) can carry */
+int sk_covariance_compute_blocks(sk_covariance* c, sk_problem* p, double* const* blocks, int n);
+int sk_covariance_get_block(const sk_covariance* c, const double* b1, const double* b2, double* out);                   /* Covariance::GetCovarianceBlock: size(b1) x size(b2) */
+int sk_covariance_get_block_in_tangent_space(const sk_covariance* c, const double* b1, const double* b2, double* out);  /* Covariance::GetCovarianceBlockInTangentSpace */
+int sk_covariance_get_matrix(const sk_covariance* c, double* const* blocks, int n, double* out);                        /* Covariance::GetCovarianceMatrix: (sum sizes)^2, listed order */
+int sk_covariance_get_matrix_in_tangent_space(const sk_covariance* c, double* const* blocks, int n, double* out);       /* Covariance::GetCovarianceMatrixInTangentSpace */
+/* (no reference counterpart) of the last compute: "columns" (N), "selected_columns" (k), "normal_matrix_pairs",
+ * "reciprocal_pivot_ratio", "phase_seconds_0".."phase_seconds_4" — device seconds from HIP events: 0 evaluation, 1 assembly and
+ * scaling, 2 factorisation, 3 extraction, 4 downloads.  SK_ERR_INVALID_ARGUMENT for another name or before a compute reached the device. */
+int sk_covariance_stat(const sk_covariance* c, const char* name, double* value);
+/* (no reference counterpart) what a binding sizes its arrays by: the size and the tangent size of a parameter block of the problem
+ * of the last successful compute (either pointer may be NULL).  SK_ERR_INVALID_ARGUMENT as for the getters. */
+int sk_covariance_block_sizes(const sk_covariance* c, const double* block, int* size, int* tangent_size);
+
 /* ---- Solver.Options (setters are ceres.i:89-92 lowerCamelCase renames) ---- */
 sk_options* sk_options_new(void);                    /* Ceres 1.x defaults, SURVEY.md §8a row a13 */
 void sk_options_free(sk_options* o);

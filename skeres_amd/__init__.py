@@ -11,6 +11,7 @@ C ABI of ``libskeres_amd.so`` (include/skeres_amd.h):
     DoubleArray, RichDoubleArray, RichDoubleMatrix CORE/RichDoubleArray.scala, RichDoubleMatrix.scala
     PredefinedLossFunctions (trivial, huber, softLOne, cauchy, tukey, tolerant, composed, scaled)  ceres.i:159-184
     Solver.Options / Solver.Summary / ceres.solve  EX/SimpleBundleAdjuster.scala:147-154
+    Covariance / Covariance.Options                ceres/covariance.h via ceres.i:29,141
 
 There is no CPU fallback: every compute call needs the HIP library and a gfx950
 device and raises otherwise.
@@ -24,7 +25,7 @@ from .api import (  # noqa: F401
     SnavelyReprojectionError, ExponentialResidual, PowellF1, PowellF2, PowellF3, PowellF4,
     BinaryScalarCost, BinaryVector3Cost, TenParameterCost, HelloCostFunctor, QuaternionRotationError,
     LocalParameterization, PredefinedLocalParameterizations,
-    PredefinedLossFunctions, LossFunction, Problem, CRSMatrix, Solver, LinearSolverType, PreconditionerType, MinimizerType, TrustRegionStrategyType, DoglegType, TerminationType,
+    PredefinedLossFunctions, LossFunction, Problem, CRSMatrix, Covariance, Solver, LinearSolverType, PreconditionerType, MinimizerType, TrustRegionStrategyType, DoglegType, TerminationType,
     ceres, StepSolver,
 )
 from . import bal  # noqa: F401

@@ -187,6 +187,21 @@ _SIGS = {
     "sk_problem_evaluate_sizes": (C.c_int, [C.c_void_p, C.c_void_p, _ip, _ip, C.POINTER(C.c_longlong)]),
     "sk_problem_evaluate_structure": (C.c_int, [C.c_void_p, C.c_void_p, _ip, _ip]),
     "sk_problem_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, _dp, _dp, _dp, _dp]),
+    "sk_covariance_options_new": (C.c_void_p, []),
+    "sk_covariance_options_free": (None, [C.c_void_p]),
+    "sk_covariance_options_set_apply_loss_function": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_covariance_options_set_min_reciprocal_condition_number": (C.c_int, [C.c_void_p, C.c_double]),
+    "sk_covariance_options_set_device": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_covariance_new": (C.c_void_p, [C.c_void_p]),
+    "sk_covariance_free": (None, [C.c_void_p]),
+    "sk_covariance_compute": (C.c_int, [C.c_void_p, C.c_void_p, _dpp, _dpp, C.c_int]),
+    "sk_covariance_compute_blocks": (C.c_int, [C.c_void_p, C.c_void_p, _dpp, C.c_int]),
+    "sk_covariance_get_block": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "sk_covariance_get_block_in_tangent_space": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "sk_covariance_get_matrix": (C.c_int, [C.c_void_p, _dpp, C.c_int, _dp]),
+    "sk_covariance_get_matrix_in_tangent_space": (C.c_int, [C.c_void_p, _dpp, C.c_int, _dp]),
+    "sk_covariance_stat": (C.c_int, [C.c_void_p, C.c_char_p, _dp]),
+    "sk_covariance_block_sizes": (C.c_int, [C.c_void_p, _dp, _ip, _ip]),
 }
 
 
@@ -217,6 +232,13 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise SkeresError("status %d: %s" % (rc, lib().sk_last_error().decode()))
+
+
+def _check_arg(rc):
+    """as _check, an invalid argument (the JVM side's require) as ValueError"""
+    if rc == 1:
+        raise ValueError(lib().sk_last_error().decode())
+    _check(rc)
 
 
 def device_count():
@@ -1265,6 +1287,101 @@ class Problem:
 
     def numResiduals(self):
         return lib().sk_problem_num_residuals(self._h)
+
+
+class Covariance:
+    """ceres::Covariance (ceres/covariance.h via ceres.i:29,141): blocks of (J^T J)^-1 at the current contents of the parameter
+    memory, by the Cholesky factorisation of the scaled normal matrix on the device.  A rank-deficient Jacobian makes compute
+    return False (there is no pseudo-inverse); blocks are DoubleArrays (or slices of one) that are parameter blocks of the problem."""
+
+    class Options:
+        """ceres::Covariance::Options: apply_loss_function (True), min_reciprocal_condition_number (1e-14)."""
+
+        def __init__(self):
+            self._h = lib().sk_covariance_options_new()
+
+        def __del__(self):
+            if getattr(self, "_h", None) and _lib is not None:
+                _lib.sk_covariance_options_free(self._h)
+                self._h = None
+
+        def applyLossFunction(self, on):
+            _check_arg(lib().sk_covariance_options_set_apply_loss_function(self._h, int(bool(on))))
+
+        def minReciprocalConditionNumber(self, v):
+            _check_arg(lib().sk_covariance_options_set_min_reciprocal_condition_number(self._h, float(v)))
+
+        def setDevice(self, device):
+            _check_arg(lib().sk_covariance_options_set_device(self._h, int(device)))
+
+    def __init__(self, options=None):
+        self._h = lib().sk_covariance_new(options._h if options is not None else None)
+        if not self._h:
+            raise SkeresError(lib().sk_last_error().decode())
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.sk_covariance_free(self._h)
+            self._h = None
+
+    @staticmethod
+    def _pp(blocks):
+        return (_dp * max(len(blocks), 1))(*[b.cast() for b in blocks])
+
+    def compute(self, pairs_or_blocks, problem):
+        """Covariance::Compute: a list of (block, block) pairs, or a list of blocks (every pair among them).  True on success,
+        False when the Jacobian is rank deficient (sk_last_error says where); raises for every other failure."""
+        items = list(pairs_or_blocks)
+        self._keep = (items, problem)
+        if items and isinstance(items[0], (tuple, list)):
+            rc = lib().sk_covariance_compute(self._h, problem._h, self._pp([a for a, _ in items]), self._pp([b for _, b in items]), len(items))
+        else:
+            rc = lib().sk_covariance_compute_blocks(self._h, problem._h, self._pp(items), len(items))
+        if rc == 5 and "rank deficient" in lib().sk_last_error().decode():
+            return False
+        _check_arg(rc)
+        return True
+
+    def lastError(self):
+        return lib().sk_last_error().decode()
+
+    def _sizes(self, block, tangent):
+        size, local = C.c_int(), C.c_int()
+        _check_arg(lib().sk_covariance_block_sizes(self._h, block.cast(), C.byref(size), C.byref(local)))
+        return local.value if tangent else size.value
+
+    def _block(self, a, b, tangent):
+        out = np.zeros((self._sizes(a, tangent), self._sizes(b, tangent)))
+        buf = np.zeros(max(out.size, 1))
+        fn = lib().sk_covariance_get_block_in_tangent_space if tangent else lib().sk_covariance_get_block
+        _check_arg(fn(self._h, a.cast(), b.cast(), buf.ctypes.data_as(_dp)))
+        out[...] = buf[:out.size].reshape(out.shape)
+        return out
+
+    def _matrix(self, blocks, tangent):
+        blocks = list(blocks)
+        dim = sum(self._sizes(b, tangent) for b in blocks)
+        buf = np.zeros(max(dim * dim, 1))
+        fn = lib().sk_covariance_get_matrix_in_tangent_space if tangent else lib().sk_covariance_get_matrix
+        _check_arg(fn(self._h, self._pp(blocks), len(blocks), buf.ctypes.data_as(_dp)))
+        return buf[:dim * dim].reshape(dim, dim).copy()
+
+    def getCovarianceBlock(self, a, b):
+        return self._block(a, b, False)
+
+    def getCovarianceBlockInTangentSpace(self, a, b):
+        return self._block(a, b, True)
+
+    def getCovarianceMatrix(self, blocks):
+        return self._matrix(blocks, False)
+
+    def getCovarianceMatrixInTangentSpace(self, blocks):
+        return self._matrix(blocks, True)
+
+    def stat(self, name):
+        v = C.c_double()
+        _check_arg(lib().sk_covariance_stat(self._h, name.encode(), C.byref(v)))
+        return v.value
 
 
 class Solver:

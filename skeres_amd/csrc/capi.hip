@@ -9,6 +9,7 @@
 #include "dense_rows_kernels.hpp"
 #include "evaluate_kernels.hpp"
 #include "cgnr_plan.hpp"
+#include "covariance.hpp"
 #include "evaluate_plan.hpp"
 #include "solver.hpp"
 
@@ -22,6 +23,8 @@ struct sk_local_parameterization { LocalParameterization p; };
 struct sk_options { Options o; };
 struct sk_summary { Summary s; };
 struct sk_solver { std::unique_ptr<SolverBase> impl; };
+struct sk_covariance_options { CovarianceOptions o; };
+struct sk_covariance { Covariance c; explicit sk_covariance(const CovarianceOptions& o) : c(o) {} };
 struct sk_evaluate_options { EvaluateOptions o; bool launch_timing = false; double launch_seconds[kEvaluatePhases] = {0, 0, 0, 0, 0, 0}; };
 
 static std::string g_program_name;
@@ -644,6 +647,79 @@ int sk_problem_evaluate(sk_problem* p, const sk_evaluate_options* o, double* cos
   if (!p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
   double* seconds = o && o->launch_timing ? const_cast<sk_evaluate_options*>(o)->launch_seconds : nullptr;
   return problem_evaluate(p->p, o ? &o->o : nullptr, cost, residuals, gradient, jacobian_values, seconds);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+
+// ---- Covariance (ceres/covariance.h via ceres.i:29,141) -------------------------------------
+sk_covariance_options* sk_covariance_options_new(void) { return new (std::nothrow) sk_covariance_options(); }
+void sk_covariance_options_free(sk_covariance_options* o) { delete o; }
+int sk_covariance_options_set_apply_loss_function(sk_covariance_options* o, int on) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.apply_loss_function = on != 0; return SK_OK;
+}
+int sk_covariance_options_set_min_reciprocal_condition_number(sk_covariance_options* o, double v) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  if (!(v >= 0.0 && v < 1.0)) { set_error("min_reciprocal_condition_number must lie in [0, 1) (got %g)", v); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.min_reciprocal_condition_number = v; return SK_OK;
+}
+int sk_covariance_options_set_device(sk_covariance_options* o, int dev) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.device = dev; return SK_OK;
+}
+sk_covariance* sk_covariance_new(const sk_covariance_options* o) {
+  SK_GUARD_BEGIN
+  return new sk_covariance(o ? o->o : CovarianceOptions());
+  SK_GUARD_END(nullptr)
+}
+void sk_covariance_free(sk_covariance* c) { delete c; }
+int sk_covariance_compute(sk_covariance* c, sk_problem* p, double* const* blocks1, double* const* blocks2, int num_pairs) {
+  SK_GUARD_BEGIN
+  if (!c || !p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return c->c.compute(p->p, blocks1, blocks2, num_pairs);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_covariance_compute_blocks(sk_covariance* c, sk_problem* p, double* const* blocks, int n) {
+  SK_GUARD_BEGIN
+  if (!c || !p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  std::vector<double*> b1, b2;
+  for (int i = 0; blocks && i < n; ++i) for (int j = i; j < n; ++j) { b1.push_back(blocks[i]); b2.push_back(blocks[j]); }
+  return c->c.compute(p->p, b1.data(), b2.data(), (int)b1.size());
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_covariance_get_block(const sk_covariance* c, const double* b1, const double* b2, double* out) {
+  SK_GUARD_BEGIN
+  if (!c) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return c->c.get_block(b1, b2, false, out);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_covariance_get_block_in_tangent_space(const sk_covariance* c, const double* b1, const double* b2, double* out) {
+  SK_GUARD_BEGIN
+  if (!c) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return c->c.get_block(b1, b2, true, out);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_covariance_get_matrix(const sk_covariance* c, double* const* blocks, int n, double* out) {
+  SK_GUARD_BEGIN
+  if (!c) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return c->c.get_matrix(blocks, n, false, out);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_covariance_get_matrix_in_tangent_space(const sk_covariance* c, double* const* blocks, int n, double* out) {
+  SK_GUARD_BEGIN
+  if (!c) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return c->c.get_matrix(blocks, n, true, out);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_covariance_block_sizes(const sk_covariance* c, const double* block, int* size, int* tangent_size) {
+  SK_GUARD_BEGIN
+  if (!c) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return c->c.block_sizes(block, size, tangent_size);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+int sk_covariance_stat(const sk_covariance* c, const char* name, double* value) {
+  SK_GUARD_BEGIN
+  if (!c) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return c->c.stat(name, value);
   SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
 

@@ -1,0 +1,369 @@
+// ceres::Covariance on the device: the host side of sk_covariance_compute.  Plan: covariance_plan.cpp; kernels: covariance_kernels.hip.
+// One compute = Problem::Evaluate's launches (its values array stays on the device), H = J^T J assembled dense (lower triangle),
+// H~ = D H D with the k selected columns as unit rows behind it, a PARTIAL factorisation of the bordered matrix by cholesky_factor
+// — H's block columns are factored, the border is left holding -Sel^T H~^-1 Sel, the selected block of the inverse, negated —,
+// the pivot ratio, the extraction of the requested blocks into one packed buffer, one download.  Everything runs on one stream,
+// launch by launch: no resident chain, no kernel that waits for another.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+
+#include "chol_kernels.hpp"
+#include "covariance.hpp"
+#include "covariance_kernels.hpp"
+#include "covariance_plan.hpp"
+#include "evaluate_kernels.hpp"
+
+namespace sk {
+
+namespace {
+struct StreamGuard {
+  hipStream_t s = nullptr;
+  ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
+};
+// device time between marks on the stream, as sk_evaluate_options_set_launch_timing does it
+struct Marks {
+  hipStream_t s = nullptr;
+  std::vector<hipEvent_t> ev;
+  void mark() { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); ev.push_back(e); } }
+  double seconds(size_t i) const {
+    float ms = 0.f;
+    return i + 1 < ev.size() && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess ? 1e-3 * ms : 0.0;
+  }
+  ~Marks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+};
+
+constexpr int kCovarianceGroup = 3;  // SYRK depth of a full factorisation in 128-column blocks (Options::cholesky_group's automatic choice)
+
+// The bordered matrix of steps 3 to 5: H (n columns, padded to npad_h) and the k border rows behind it.
+struct Bordered {
+  int n = 0, npad_h = 0, k = 0, npad = 0;
+  long ld = 0;
+  DevBuf<double> S, Linv, d, ratio;
+  DevBuf<int> zero_col, info, sel_col;
+  double* border() const { return S.p + (long)npad_h * ld + npad_h; }
+  // S zeroed (the assembly stores every structural non-zero of the lower triangle once)
+  int alloc(int n_, const std::vector<int>& sel, hipStream_t s) {
+    n = n_; k = (int)sel.size();
+    npad_h = std::max(1, (n + 127) / 128) * 128;
+    npad = npad_h + std::max(1, (k + 127) / 128) * 128;
+    ld = npad;
+    SK_HIP_TRY(S.alloc((size_t)npad * npad)); SK_HIP_TRY(S.zero(s));
+    SK_HIP_TRY(Linv.alloc((size_t)npad_h * 128)); SK_HIP_TRY(Linv.zero(s));
+    SK_HIP_TRY(d.alloc((size_t)npad_h)); SK_HIP_TRY(ratio.alloc(2)); SK_HIP_TRY(ratio.zero(s));
+    SK_HIP_TRY(info.alloc(1)); SK_HIP_TRY(info.zero(s));
+    const std::vector<int> none(1, INT_MAX);
+    SK_HIP_TRY(zero_col.upload(none, s));
+    std::vector<int> sc = sel; if (sc.empty()) sc.push_back(0);
+    SK_HIP_TRY(sel_col.upload(sc, s));
+    SK_HIP_TRY(hipStreamSynchronize(s));  // (`none` and `sc` go out of scope)
+    return SK_OK;
+  }
+  // steps 3 to 5; *zero: the first column with an exactly zero diagonal entry (INT_MAX: none — then the matrix was factored)
+  int scale_and_factor(hipStream_t s, int* zero, Marks* marks) {
+    launch_cov_scale(S.p, ld, n, npad_h, d.p, zero_col.p, sel_col.p, k, s);
+    SK_HIP_TRY(hipGetLastError());
+    if (marks) marks->mark();
+    SK_HIP_TRY(hipMemcpyAsync(zero, zero_col.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipStreamSynchronize(s));
+    if (*zero != INT_MAX) return SK_OK;
+    SK_HIP_TRY(cholesky_init());
+    cholesky_factor(S.p, ld, npad, Linv.p, info.p, kCovarianceGroup, s, /*ctx*/ nullptr, /*kt*/ nullptr, /*last*/ nullptr, /*allow_chain*/ false,
+                    /*ncols*/ npad_h / 128, /*tail_rows*/ (npad - npad_h) / 128);
+    launch_cov_pivot_ratio(S.p, ld, n, ratio.p, s);
+    SK_HIP_TRY(hipGetLastError());
+    if (marks) marks->mark();
+    return SK_OK;
+  }
+};
+}  // namespace
+
+int Covariance::compute(const Problem& p, double* const* blocks1, double* const* blocks2, int num_pairs) {
+  valid_ = false; has_stats_ = false;
+  if (num_pairs <= 0 || !blocks1 || !blocks2) { set_error("Covariance: no covariance blocks were asked for"); return SK_ERR_INVALID_ARGUMENT; }
+  std::vector<std::pair<int, int>> pairs;
+  for (int i = 0; i < num_pairs; ++i) {
+    auto a = p.block_of.find(blocks1[i]), b = p.block_of.find(blocks2[i]);
+    if (a == p.block_of.end() || b == p.block_of.end()) {
+      set_error("Covariance: block %d of pair %d is no parameter block of the problem", a == p.block_of.end() ? 1 : 2, i);
+      return SK_ERR_INVALID_ARGUMENT;
+    }
+    pairs.emplace_back(a->second, b->second);
+  }
+  return run(p, pairs);
+}
+
+int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pairs) {
+  CovariancePlan C;
+  std::string why;
+  int rc = covariance_plan_build(p, pairs, &C, &why);
+  if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return SK_ERR_NO_DEVICE; }
+  if (opt_.device >= 0) SK_HIP_TRY(hipSetDevice(opt_.device));
+  const EvaluatePlan& E = C.eval;
+  const int num_pb = (int)p.block_ptr.size(), N = C.num_cols;
+
+  // step 1: the evaluation, by Problem::Evaluate's own code; the values array stays where it is
+  EvaluateOptions eo;
+  eo.apply_loss_function = opt_.apply_loss_function; eo.device = opt_.device;
+  double eval_seconds[kEvaluatePhases] = {0, 0, 0, 0, 0, 0};
+  DevBuf<double> d_val;
+  rc = problem_evaluate(p, &eo, nullptr, nullptr, nullptr, nullptr, eval_seconds, &d_val);
+  if (rc != SK_OK) return rc;
+
+  // the point (for the Plus-Jacobians of the lift) and the parameter blocks as the extraction reads them
+  std::vector<double> x((size_t)std::max(C.block_off[num_pb], 1), 0.0);
+  std::vector<ParamBlock> pblocks((size_t)std::max(num_pb, 1));
+  for (int b = 0; b < num_pb; ++b) {
+    std::memcpy(&x[C.block_off[b]], p.block_ptr[b], p.block_size[b] * sizeof(double));
+    ParamBlock& pb = pblocks[b];
+    pb.type = C.pb_type[b]; pb.global_size = C.pb_size[b]; pb.local_size = C.pb_local_size[b];
+    pb.constant_mask = C.pb_mask[b]; pb.global_off = C.block_off[b]; pb.local_off = C.pb_local_off[b];
+  }
+  auto padded = [](std::vector<int> v) { if (v.empty()) v.push_back(0); return v; };
+  auto padded_l = [](std::vector<long> v) { if (v.empty()) v.push_back(0); return v; };
+
+  StreamGuard sg;
+  SK_HIP_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  hipStream_t s = sg.s;
+  DevBuf<int> d_val_off, d_row_off, d_slot_owner, d_slot_pos, d_part_pair, d_part_begin, d_part_end, d_part_out, d_long_pair, d_long_begin, d_pair_i, d_pair_j,
+      d_term_si, d_term_sj, d_cb_col, d_cb_size, d_ra, d_rb, d_a, d_b;
+  DevBuf<long> d_tan_off, d_amb_off;
+  DevBuf<double> d_x, d_partial, d_out;
+  DevBuf<ParamBlock> d_pblocks;
+  SK_HIP_TRY(d_val_off.upload(E.val_off, s)); SK_HIP_TRY(d_row_off.upload(E.row_off, s));
+  SK_HIP_TRY(d_slot_owner.upload(padded(E.slot_owner), s)); SK_HIP_TRY(d_slot_pos.upload(padded(E.slot_pos), s));
+  SK_HIP_TRY(d_part_pair.upload(padded(C.part_pair), s)); SK_HIP_TRY(d_part_begin.upload(padded(C.part_begin), s));
+  SK_HIP_TRY(d_part_end.upload(padded(C.part_end), s)); SK_HIP_TRY(d_part_out.upload(padded(C.part_out), s));
+  SK_HIP_TRY(d_long_pair.upload(padded(C.long_pair), s)); SK_HIP_TRY(d_long_begin.upload(C.long_begin, s));
+  SK_HIP_TRY(d_pair_i.upload(padded(C.pair_i), s)); SK_HIP_TRY(d_pair_j.upload(padded(C.pair_j), s));
+  SK_HIP_TRY(d_term_si.upload(padded(C.term_si), s)); SK_HIP_TRY(d_term_sj.upload(padded(C.term_sj), s));
+  SK_HIP_TRY(d_cb_col.upload(padded(C.cb_col), s)); SK_HIP_TRY(d_cb_size.upload(padded(C.cb_size), s));
+  SK_HIP_TRY(d_ra.upload(padded(C.req_ra), s)); SK_HIP_TRY(d_rb.upload(padded(C.req_rb), s));
+  SK_HIP_TRY(d_a.upload(padded(C.req_a), s)); SK_HIP_TRY(d_b.upload(padded(C.req_b), s));
+  SK_HIP_TRY(d_tan_off.upload(padded_l(C.req_tan_off), s)); SK_HIP_TRY(d_amb_off.upload(padded_l(C.req_amb_off), s));
+  SK_HIP_TRY(d_x.upload(x, s)); SK_HIP_TRY(d_pblocks.upload(pblocks, s));
+  SK_HIP_TRY(d_partial.alloc((size_t)std::max(C.num_partials, 1) * kCovarianceTile));
+  SK_HIP_TRY(d_out.alloc((size_t)std::max<long>(C.out_size, 1))); SK_HIP_TRY(d_out.zero(s));
+  SK_HIP_TRY(hipStreamSynchronize(s));  // (the padded copies above are temporaries)
+
+  stats_.clear();
+  stats_["columns"] = N; stats_["selected_columns"] = C.k; stats_["normal_matrix_pairs"] = (double)C.pair_i.size();
+  stats_["reciprocal_pivot_ratio"] = 0.0;
+  double phase[kCovariancePhases] = {0, 0, 0, 0, 0};
+  for (int i = 1; i <= 2; ++i) phase[0] += eval_seconds[i];  // (the evaluation launches and the finish: what produces the values array)
+  auto keep_stats = [&] {
+    for (int i = 0; i < kCovariancePhases; ++i) stats_["phase_seconds_" + std::to_string(i)] = phase[i];
+    has_stats_ = true;
+  };
+
+  Marks marks; marks.s = s;
+  marks.mark();
+  Bordered B;
+  rc = B.alloc(N, C.sel_col, s);
+  if (rc != SK_OK) return rc;
+  // step 2: the normal matrix
+  CovJac J{d_val.p, d_val_off.p, d_row_off.p, d_slot_owner.p, d_slot_pos.p};
+  CovPairs P;
+  P.num_parts = (int)C.part_pair.size(); P.num_long = (int)C.long_pair.size();
+  P.part_pair = d_part_pair.p; P.part_begin = d_part_begin.p; P.part_end = d_part_end.p; P.part_out = d_part_out.p;
+  P.long_pair = d_long_pair.p; P.long_begin = d_long_begin.p; P.pair_i = d_pair_i.p; P.pair_j = d_pair_j.p;
+  P.term_si = d_term_si.p; P.term_sj = d_term_sj.p; P.cb_col = d_cb_col.p; P.cb_size = d_cb_size.p;
+  launch_cov_normal_assemble(J, P, B.S.p, B.ld, d_partial.p, s);
+  // steps 3 to 5
+  int zero = INT_MAX;
+  rc = B.scale_and_factor(s, &zero, &marks);
+  if (rc != SK_OK) return rc;
+  phase[1] = marks.seconds(0);
+  if (zero != INT_MAX) {
+    int cb = 0;
+    while (cb + 1 < (int)C.cb_col.size() && C.cb_col[cb + 1] <= zero) ++cb;
+    keep_stats();
+    set_error("Covariance: the Jacobian is rank deficient: column %d (parameter block %d, coordinate %d of its tangent space) is zero — no residual block depends on it",
+              zero, C.cb_block[cb], zero - C.cb_col[cb]);
+    return SK_ERR_EVALUATION_FAILED;
+  }
+  // step 6: the requested blocks, one packed buffer, one download
+  CovRequests R;
+  R.num = (int)C.req_a.size(); R.ra = d_ra.p; R.rb = d_rb.p; R.a = d_a.p; R.b = d_b.p; R.tan_off = d_tan_off.p; R.amb_off = d_amb_off.p;
+  R.pblocks = d_pblocks.p; R.x = d_x.p;
+  launch_cov_extract(R, B.border(), B.ld, B.d.p, d_out.p, s);
+  SK_HIP_TRY(hipGetLastError());
+  marks.mark();
+  std::vector<double> out((size_t)std::max<long>(C.out_size, 1));
+  double ratio[2] = {0, 0};
+  int info = 0;
+  SK_HIP_TRY(hipMemcpyAsync(out.data(), d_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(ratio, B.ratio.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(&info, B.info.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  marks.mark();
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  phase[2] = marks.seconds(1); phase[3] = marks.seconds(2); phase[4] = marks.seconds(3);
+  const double rcond = N == 0 ? 1.0 : ratio[1] > 0.0 && std::isfinite(ratio[0]) && std::isfinite(ratio[1]) ? ratio[0] / ratio[1] : 0.0;  // (N == 0: every block is constant)
+  stats_["reciprocal_pivot_ratio"] = rcond;
+  keep_stats();
+  if (info != 0 || (N > 0 && (!(ratio[0] > 0.0) || !std::isfinite(ratio[1])))) {
+    set_error("Covariance: the Jacobian is rank deficient: the factorisation of J^T J met a pivot that is not positive");
+    return SK_ERR_EVALUATION_FAILED;
+  }
+  if (rcond < opt_.min_reciprocal_condition_number) {
+    set_error("Covariance: the Jacobian is rank deficient: pivot ratio min L_jj^2 / max L_jj^2 = %.3e of the scaled normal matrix is below min_reciprocal_condition_number = %.3e",
+              rcond, opt_.min_reciprocal_condition_number);
+    return SK_ERR_EVALUATION_FAILED;
+  }
+
+  block_of_.clear();
+  for (int b = 0; b < num_pb; ++b) block_of_[p.block_ptr[b]] = b;
+  size_ = C.pb_size; tangent_ = C.pb_local_size;
+  req_of_.clear();
+  for (size_t r = 0; r < C.req_a.size(); ++r) req_of_[{C.req_a[r], C.req_b[r]}] = (int)r;
+  tan_off_ = C.req_tan_off; amb_off_ = C.req_amb_off;
+  out_.swap(out);
+  valid_ = true;
+  return SK_OK;
+}
+
+int Covariance::get_block(const double* b1, const double* b2, bool tangent, double* out) const {
+  if (!valid_) { set_error("Covariance: no covariance has been computed (call compute first; a failed compute leaves none)"); return SK_ERR_INVALID_ARGUMENT; }
+  if (!out) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  auto a = block_of_.find(b1), b = block_of_.find(b2);
+  if (a == block_of_.end() || b == block_of_.end()) { set_error("Covariance: not a parameter block of the problem the covariance was computed for"); return SK_ERR_INVALID_ARGUMENT; }
+  const int ia = a->second, ib = b->second;
+  auto r = req_of_.find({std::min(ia, ib), std::max(ia, ib)});
+  if (r == req_of_.end()) { set_error("Covariance: the covariance of parameter blocks %d and %d was not computed", ia, ib); return SK_ERR_INVALID_ARGUMENT; }
+  const std::vector<int>& sz = tangent ? tangent_ : size_;
+  const double* src = out_.data() + (tangent ? tan_off_ : amb_off_)[r->second];
+  const int rows = sz[ia], cols = sz[ib];
+  if (ia <= ib) { std::memcpy(out, src, (size_t)rows * cols * sizeof(double)); return SK_OK; }
+  for (int i = 0; i < rows; ++i) for (int j = 0; j < cols; ++j) out[(size_t)i * cols + j] = src[(size_t)j * rows + i];  // stored as (ib, ia)
+  return SK_OK;
+}
+
+int Covariance::get_matrix(double* const* blocks, int n, bool tangent, double* out) const {
+  if (!valid_) { set_error("Covariance: no covariance has been computed (call compute first; a failed compute leaves none)"); return SK_ERR_INVALID_ARGUMENT; }
+  if (n <= 0 || !blocks || !out) { set_error("Covariance: bad arguments"); return SK_ERR_INVALID_ARGUMENT; }
+  const std::vector<int>& sz = tangent ? tangent_ : size_;
+  std::vector<int> idx(n), off(n + 1, 0);
+  for (int i = 0; i < n; ++i) {
+    auto it = block_of_.find(blocks[i]);
+    if (it == block_of_.end()) { set_error("Covariance: blocks[%d] is no parameter block of the problem the covariance was computed for", i); return SK_ERR_INVALID_ARGUMENT; }
+    idx[i] = it->second; off[i + 1] = off[i] + sz[idx[i]];
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j)
+      if (!req_of_.count({std::min(idx[i], idx[j]), std::max(idx[i], idx[j])})) {
+        set_error("Covariance: the covariance of blocks[%d] and blocks[%d] was not computed", i, j);
+        return SK_ERR_INVALID_ARGUMENT;
+      }
+  const size_t dim = (size_t)off[n];
+  double tile[kCovarianceTile];
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {
+      const int rc = get_block(blocks[i], blocks[j], tangent, tile);
+      if (rc != SK_OK) return rc;
+      const int rows = sz[idx[i]], cols = sz[idx[j]];
+      for (int a = 0; a < rows; ++a) std::memcpy(out + (size_t)(off[i] + a) * dim + off[j], tile + (size_t)a * cols, (size_t)cols * sizeof(double));
+    }
+  return SK_OK;
+}
+
+int Covariance::block_sizes(const double* block, int* size, int* tangent_size) const {
+  if (!valid_) { set_error("Covariance: no covariance has been computed (call compute first; a failed compute leaves none)"); return SK_ERR_INVALID_ARGUMENT; }
+  auto it = block_of_.find(block);
+  if (it == block_of_.end()) { set_error("Covariance: not a parameter block of the problem the covariance was computed for"); return SK_ERR_INVALID_ARGUMENT; }
+  if (size) *size = size_[it->second];
+  if (tangent_size) *tangent_size = tangent_[it->second];
+  return SK_OK;
+}
+
+int Covariance::stat(const char* name, double* value) const {
+  if (!name || !value) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  auto it = stats_.find(name);
+  if (!has_stats_ || it == stats_.end()) { set_error("Covariance: no stat \"%s\" (%s)", name, has_stats_ ? "unknown name" : "nothing has been computed"); return SK_ERR_INVALID_ARGUMENT; }
+  *value = it->second;
+  return SK_OK;
+}
+
+int covariance_border_route(int n, const double* H, int block, const int* sel_blocks, int num_sel, double* out, double* ratio_out) {
+  if (n <= 0 || !H || block <= 0 || block > kCovarianceMaxBlock || !sel_blocks || num_sel <= 0 || !out) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return SK_ERR_NO_DEVICE; }
+  const int nblocks = (n + block - 1) / block;
+  std::vector<ParamBlock> pblocks(nblocks);
+  for (int b = 0; b < nblocks; ++b) {
+    ParamBlock& pb = pblocks[b];
+    pb.type = kParamIdentity; pb.global_size = pb.local_size = std::min(block, n - b * block);
+    pb.constant_mask = 0u; pb.global_off = pb.local_off = b * block;
+  }
+  std::vector<int> sel_col, sel_off(1, 0), ra, rb, a, b;
+  std::vector<long> tan_off, amb_off;
+  for (int i = 0; i < num_sel; ++i) {
+    if (sel_blocks[i] < 0 || sel_blocks[i] >= nblocks) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
+    for (int j = 0; j < i; ++j) if (sel_blocks[j] == sel_blocks[i]) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
+    for (int j = 0; j < pblocks[sel_blocks[i]].local_size; ++j) sel_col.push_back(sel_blocks[i] * block + j);
+    sel_off.push_back((int)sel_col.size());
+  }
+  const int k = (int)sel_col.size();
+  long out_size = 0;
+  for (int i = 0; i < num_sel; ++i)
+    for (int j = 0; j <= i; ++j) {  // the lower block triangle, mirrored below
+      ra.push_back(sel_off[i]); rb.push_back(sel_off[j]); a.push_back(sel_blocks[i]); b.push_back(sel_blocks[j]);
+      const long sz = (long)pblocks[sel_blocks[i]].local_size * pblocks[sel_blocks[j]].local_size;
+      tan_off.push_back(out_size); out_size += sz;
+      amb_off.push_back(out_size); out_size += sz;
+    }
+  StreamGuard sg;
+  SK_HIP_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+  hipStream_t s = sg.s;
+  Bordered B;
+  int rc = B.alloc(n, sel_col, s);
+  if (rc != SK_OK) return rc;
+  std::vector<double> lower((size_t)n * n, 0.0);  // (what the assembly leaves: the lower triangle, zeros above it)
+  for (int i = 0; i < n; ++i) std::memcpy(&lower[(size_t)i * n], H + (size_t)i * n, (size_t)(i + 1) * sizeof(double));
+  SK_HIP_TRY(hipMemcpy2DAsync(B.S.p, (size_t)B.ld * sizeof(double), lower.data(), (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)n, hipMemcpyHostToDevice, s));
+  DevBuf<int> d_ra, d_rb, d_a, d_b; DevBuf<long> d_tan_off, d_amb_off; DevBuf<double> d_x, d_out; DevBuf<ParamBlock> d_pblocks;
+  const std::vector<double> x((size_t)n, 0.0);
+  SK_HIP_TRY(d_ra.upload(ra, s)); SK_HIP_TRY(d_rb.upload(rb, s)); SK_HIP_TRY(d_a.upload(a, s)); SK_HIP_TRY(d_b.upload(b, s));
+  SK_HIP_TRY(d_tan_off.upload(tan_off, s)); SK_HIP_TRY(d_amb_off.upload(amb_off, s)); SK_HIP_TRY(d_x.upload(x, s)); SK_HIP_TRY(d_pblocks.upload(pblocks, s));
+  SK_HIP_TRY(d_out.alloc((size_t)out_size)); SK_HIP_TRY(d_out.zero(s));
+  int zero = INT_MAX;
+  rc = B.scale_and_factor(s, &zero, nullptr);
+  if (rc != SK_OK) return rc;
+  if (zero != INT_MAX) { set_error("a diagonal entry is zero (column %d)", zero); return SK_ERR_EVALUATION_FAILED; }
+  CovRequests R;
+  R.num = (int)ra.size(); R.ra = d_ra.p; R.rb = d_rb.p; R.a = d_a.p; R.b = d_b.p; R.tan_off = d_tan_off.p; R.amb_off = d_amb_off.p; R.pblocks = d_pblocks.p; R.x = d_x.p;
+  launch_cov_extract(R, B.border(), B.ld, B.d.p, d_out.p, s);
+  SK_HIP_TRY(hipGetLastError());
+  std::vector<double> packed((size_t)out_size);
+  double ratio[2] = {0, 0};
+  int info = 0;
+  SK_HIP_TRY(hipMemcpyAsync(packed.data(), d_out.p, packed.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(ratio, B.ratio.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(&info, B.info.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  if (info != 0) { set_error("matrix is not positive definite"); return SK_ERR_EVALUATION_FAILED; }
+  if (ratio_out) *ratio_out = ratio[1] > 0.0 ? ratio[0] / ratio[1] : 0.0;
+  size_t r = 0;
+  for (int i = 0; i < num_sel; ++i)
+    for (int j = 0; j <= i; ++j, ++r) {
+      const int rows = pblocks[sel_blocks[i]].local_size, cols = pblocks[sel_blocks[j]].local_size;
+      const double* t = packed.data() + amb_off[r];  // (identity blocks: the lift is a copy — the route is checked through it)
+      for (int p = 0; p < rows; ++p)
+        for (int q = 0; q < cols; ++q) {
+          out[(size_t)(sel_off[i] + p) * k + sel_off[j] + q] = t[(size_t)p * cols + q];
+          out[(size_t)(sel_off[j] + q) * k + sel_off[i] + p] = t[(size_t)p * cols + q];
+        }
+    }
+  return SK_OK;
+}
+
+}  // namespace sk
+
+#ifdef SK_TESTING
+// the testing library's entry to steps 3 to 6 (libskeres_amd_testing.so only; not part of include/skeres_amd.h)
+extern "C" int sk_testing_covariance_border_route(int n, const double* H, int block, const int* sel_blocks, int num_sel, double* out, double* ratio) {
+  try { return sk::covariance_border_route(n, H, block, sel_blocks, num_sel, out, ratio); }
+  catch (...) { sk::set_error("internal error"); return SK_ERR_INVALID_ARGUMENT; }
+}
+#endif

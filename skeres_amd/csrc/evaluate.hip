@@ -25,15 +25,15 @@ struct Marks {
 }  // namespace
 
 int problem_evaluate(const Problem& p, const EvaluateOptions* options, double* cost, double* residuals, double* gradient, double* values,
-                     double* launch_seconds) {
-  const bool want_jac = gradient || values;
+                     double* launch_seconds, DevBuf<double>* keep_values) {
+  const bool want_jac = gradient || values || keep_values;
   EvaluatePlan P;
   std::string why;
   int rc = evaluate_plan_build(p, options, false, gradient != nullptr, want_jac, &P, &why);
   if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return SK_ERR_NO_DEVICE; }
-  if (!cost && !residuals && !gradient && !values) return SK_OK;
+  if (!cost && !residuals && !gradient && !values && !keep_values) return SK_OK;
   if (options && options->device >= 0) SK_HIP_TRY(hipSetDevice(options->device));
   const bool apply_loss = !options || options->apply_loss_function;
   const int nb = (int)P.blocks.size(), num_pb = (int)p.block_ptr.size();
@@ -183,6 +183,7 @@ int problem_evaluate(const Problem& p, const EvaluateOptions* options, double* c
     }
   }
   if (failed) { set_error("Evaluate: a cost functor reported failure"); return SK_ERR_EVALUATION_FAILED; }
+  if (keep_values) { keep_values->release(); keep_values->p = d_val.p; keep_values->n = d_val.n; d_val.p = nullptr; d_val.n = 0; }  // (the caller's from here on)
   return SK_OK;
 }
 

@@ -3,7 +3,8 @@
     python -m skeres_amd.examples.simple_bundle_adjuster <data_file.txt> [--recorded]
 
 Reads a BAL text file (SimpleBundleAdjuster.scala:37-76), adds one residual block per observation
-with a shared trivial loss, solves with DENSE_SCHUR and prints the full report.
+with a shared trivial loss, solves with DENSE_SCHUR and prints the full report.  On a small problem (up to 32 768 columns: the dense
+covariance path) it then prints how well the minimum determines one camera: the standard deviations of camera 2 from sk.Covariance.
 --recorded: the functor is the generic body of examples/traced_functors.py, recorded once and interpreted on the
 device, instead of the body registered in the device functor registry (what a user's own functor goes through)."""
 import sys
@@ -46,7 +47,26 @@ def main(argv):
     sk.ceres.solve(options, problem, summary)
     print(summary.fullReport())
     print("Reprojection RMS after: %.6f px" % rms())
+    camera_standard_deviations(problem, cameras, bal_problem)
     return 0
+
+
+def camera_standard_deviations(problem, cameras, bal_problem, camera=2):
+    """The square roots of the diagonal of camera 2's covariance block at the minimum.  Cameras 0 and 1 are held constant for this:
+    bundle adjustment has a gauge freedom (a similarity transform of the whole scene changes no residual), so with every camera
+    free J^T J is singular and Covariance.compute reports a rank-deficient Jacobian; two fixed cameras fix the gauge."""
+    if bal_problem.num_cameras <= camera or 9 * (bal_problem.num_cameras - 2) + 3 * bal_problem.num_points > 32768:
+        return None
+    for held in (0, 1):
+        problem.setParameterBlockConstant(cameras.slice(9 * held))
+    block = cameras.slice(9 * camera)
+    covariance = sk.Covariance(sk.Covariance.Options())
+    if not covariance.compute([(block, block)], problem):
+        print("Covariance: " + covariance.lastError())
+        return None
+    sigma = [float(v) ** 0.5 for v in covariance.getCovarianceBlock(block, block).diagonal()]
+    print("Camera %d standard deviations (cameras 0 and 1 held): %s" % (camera, " ".join("%.3e" % v for v in sigma)))
+    return sigma
 
 
 if __name__ == "__main__":
