@@ -86,6 +86,7 @@ public final class SkeresNative {
   public static native double skProblemGetParameterUpperBound(long p, long values, int index);
   public static native int skProblemNumResidualBlocks(long p);
   public static native int skProblemNumParameterBlocks(long p);
+  public static native int skProblemParameterBlockIndex(long p, long values);
   public static native int skProblemNumParameters(long p);
   public static native int skProblemNumResiduals(long p);
   // ceres::Problem::Evaluate (ceres/problem.h, ceres/crs_matrix.h via ceres.i); options may be 0 (defaults), output arrays null
@@ -105,6 +106,9 @@ public final class SkeresNative {
   public static native int skCovarianceOptionsSetApplyLossFunction(long o, int on);
   public static native int skCovarianceOptionsSetMinReciprocalConditionNumber(long o, double v);
   public static native int skCovarianceOptionsSetDevice(long o, int device);
+  public static native int skCovarianceOptionsSetSchurElimination(long o, int on);
+  // ofBlock: [parameter blocks] or null (1 in E, 0 in F, -1 constant / no columns); counts: {eliminated blocks, reduced columns}; terms: {Schur terms}
+  public static native int skCovarianceEliminationPlan(long p, int[] ofBlock, int[] counts, long[] terms);
   public static native long skCovarianceNew(long o);
   public static native void skCovarianceFree(long c);
   public static native int skCovarianceCompute(long c, long p, long[] blocks1, long[] blocks2);

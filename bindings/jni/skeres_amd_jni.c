@@ -285,6 +285,7 @@ SK_JNI(jdouble, skProblemGetParameterLowerBound)(JNIEnv* env, jclass c, jlong p,
 SK_JNI(jdouble, skProblemGetParameterUpperBound)(JNIEnv* env, jclass c, jlong p, jlong values, jint index) { (void)env; (void)c; return sk_problem_get_parameter_upper_bound(PTR(sk_problem, p), PTR(double, values), index); }
 SK_JNI(jint, skProblemNumResidualBlocks)(JNIEnv* env, jclass c, jlong p) { (void)env; (void)c; return sk_problem_num_residual_blocks(PTR(sk_problem, p)); }
 SK_JNI(jint, skProblemNumParameterBlocks)(JNIEnv* env, jclass c, jlong p) { (void)env; (void)c; return sk_problem_num_parameter_blocks(PTR(sk_problem, p)); }
+SK_JNI(jint, skProblemParameterBlockIndex)(JNIEnv* env, jclass c, jlong p, jlong values) { (void)env; (void)c; return sk_problem_parameter_block_index(PTR(sk_problem, p), PTR(double, values)); }
 SK_JNI(jint, skProblemNumParameters)(JNIEnv* env, jclass c, jlong p) { (void)env; (void)c; return sk_problem_num_parameters(PTR(sk_problem, p)); }
 SK_JNI(jint, skProblemNumResiduals)(JNIEnv* env, jclass c, jlong p) { (void)env; (void)c; return sk_problem_num_residuals(PTR(sk_problem, p)); }
 
@@ -452,6 +453,25 @@ SK_JNI(void, skCovarianceOptionsFree)(JNIEnv* env, jclass c, jlong o) { (void)en
 SK_JNI(jint, skCovarianceOptionsSetApplyLossFunction)(JNIEnv* env, jclass c, jlong o, jint on) { (void)c; return check(env, sk_covariance_options_set_apply_loss_function(PTR(sk_covariance_options, o), on)); }
 SK_JNI(jint, skCovarianceOptionsSetMinReciprocalConditionNumber)(JNIEnv* env, jclass c, jlong o, jdouble v) { (void)c; return check(env, sk_covariance_options_set_min_reciprocal_condition_number(PTR(sk_covariance_options, o), v)); }
 SK_JNI(jint, skCovarianceOptionsSetDevice)(JNIEnv* env, jclass c, jlong o, jint device) { (void)c; return check(env, sk_covariance_options_set_device(PTR(sk_covariance_options, o), device)); }
+SK_JNI(jint, skCovarianceOptionsSetSchurElimination)(JNIEnv* env, jclass c, jlong o, jint on) { (void)c; return check(env, sk_covariance_options_set_schur_elimination(PTR(sk_covariance_options, o), on)); }
+/* ofBlock: [parameter blocks] or null; counts: {eliminated blocks, reduced columns}; terms: {Schur terms} */
+SK_JNI(jint, skCovarianceEliminationPlan)(JNIEnv* env, jclass c, jlong p, jintArray ofBlock, jintArray counts, jlongArray terms) {
+  (void)c;
+  int n = 0, cols = 0;
+  long long t = 0;
+  jint* of = ofBlock ? (*env)->GetIntArrayElements(env, ofBlock, NULL) : NULL;
+  const int rc = sk_covariance_elimination_plan(PTR(sk_problem, p), (int*)of, &n, &cols, &t);
+  if (of) (*env)->ReleaseIntArrayElements(env, ofBlock, of, 0);
+  if (rc == SK_OK) {
+    jint* k = (*env)->GetIntArrayElements(env, counts, NULL);
+    k[0] = n; k[1] = cols;
+    (*env)->ReleaseIntArrayElements(env, counts, k, 0);
+    jlong* l = (*env)->GetLongArrayElements(env, terms, NULL);
+    l[0] = (jlong)t;
+    (*env)->ReleaseLongArrayElements(env, terms, l, 0);
+  }
+  return check(env, rc);
+}
 SK_JNI(jlong, skCovarianceNew)(JNIEnv* env, jclass c, jlong o) { (void)c; return check_handle(env, sk_covariance_new(PTR(sk_covariance_options, o))); }
 SK_JNI(void, skCovarianceFree)(JNIEnv* env, jclass c, jlong v) { (void)env; (void)c; sk_covariance_free(PTR(sk_covariance, v)); }
 /* the native addresses of n parameter blocks as a double*[] (NULL: out of memory) */

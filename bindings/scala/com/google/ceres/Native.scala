@@ -151,6 +151,8 @@ class CeresProblem(options: CeresProblem.Options) {
   def getParameterUpperBound(values: DoublePointer, index: Int): Double = SkeresNative.skProblemGetParameterUpperBound(handle, values.address, index)
   def numResidualBlocks: Int = SkeresNative.skProblemNumResidualBlocks(handle)
   def numParameterBlocks: Int = SkeresNative.skProblemNumParameterBlocks(handle)
+  /** (no reference counterpart) the block's index in the problem's own order (first mention), -1 when it is none of its blocks */
+  def parameterBlockIndex(block: DoublePointer): Int = SkeresNative.skProblemParameterBlockIndex(handle, block.address)
   def numParameters: Int = SkeresNative.skProblemNumParameters(handle)
   def numResiduals: Int = SkeresNative.skProblemNumResiduals(handle)
   /** ceres::Problem::Evaluate (ceres/problem.h via ceres.i) at the current contents of the parameter memory, on the device: the cost,
@@ -228,7 +230,8 @@ class Covariance(options: Covariance.Options) {
   def getCovarianceBlockInTangentSpace(a: DoublePointer, b: DoublePointer): Array[Double] = block(a, b, true)
   def getCovarianceMatrix(blocks: Seq[DoublePointer]): Array[Double] = matrix(blocks, false)
   def getCovarianceMatrixInTangentSpace(blocks: Seq[DoublePointer]): Array[Double] = matrix(blocks, true)
-  /** "columns", "selected_columns", "normal_matrix_pairs", "reciprocal_pivot_ratio", "phase_seconds_0".."phase_seconds_4" of the last compute */
+  /** "columns", "selected_columns", "normal_matrix_pairs", "reciprocal_pivot_ratio", "schur_elimination", "eliminated_blocks", "reduced_columns",
+    * "schur_terms", "phase_seconds_0".."phase_seconds_4" of the last compute */
   def stat(name: String): Double = SkeresNative.skCovarianceStat(handle, name)
   override def finalize(): Unit = SkeresNative.skCovarianceFree(handle)
 }
@@ -239,7 +242,19 @@ object Covariance {
     def setApplyLossFunction(on: Boolean): Unit = SkeresNative.skCovarianceOptionsSetApplyLossFunction(handle, if (on) 1 else 0)
     def setMinReciprocalConditionNumber(v: Double): Unit = SkeresNative.skCovarianceOptionsSetMinReciprocalConditionNumber(handle, v)
     def setDevice(device: Int): Unit = SkeresNative.skCovarianceOptionsSetDevice(handle, device)
+    /** (no reference counterpart; default off) eliminate an independent set of blocks — in bundle adjustment the points — in front of
+      * the dense factorisation: the route for problems of more than 32 768 columns (include/skeres_amd.h). */
+    def setSchurElimination(on: Boolean): Unit = SkeresNative.skCovarianceOptionsSetSchurElimination(handle, if (on) 1 else 0)
     override def finalize(): Unit = SkeresNative.skCovarianceOptionsFree(handle)
+  }
+  /** The eliminated set of setSchurElimination for this problem, from host data alone (sk_covariance_elimination_plan). */
+  class EliminationPlan(val eliminatedOfBlock: Array[Int], val numEliminated: Int, val reducedColumns: Int, val schurTerms: Long)
+  def eliminationPlan(problem: CeresProblem): EliminationPlan = {
+    val ofBlock = new Array[Int](math.max(1, problem.numParameterBlocks))
+    val counts = new Array[Int](2)
+    val terms = new Array[Long](1)
+    SkeresNative.skCovarianceEliminationPlan(problem.handle, ofBlock, counts, terms)
+    new EliminationPlan(ofBlock.take(problem.numParameterBlocks), counts(0), counts(1), terms(0))
   }
 }
 

@@ -54,7 +54,8 @@ void initGoogleLogging(const char* name) { sk_init_logging(name); }
 // (sk_evaluate_options_* and sk_problem_evaluate / _sizes / _structure too: ceres::Problem::Evaluate and ceres::CRSMatrix, which the reference's
 // ceres.i %include's with ceres/problem.h and ceres/crs_matrix.h; CeresProblem.evaluate in Native.scala binds them by hand over Java arrays)
 // (sk_covariance_options_* and sk_covariance_* too: ceres::Covariance and ceres::Covariance::Options, which the reference's ceres.i #include's and
-// %include's with ceres/covariance.h, ceres.i:29,141; Covariance in Native.scala binds them by hand over Java arrays)
+// %include's with ceres/covariance.h, ceres.i:29,141; Covariance in Native.scala binds them by hand over Java arrays;
+// sk_covariance_options_set_schur_elimination, sk_covariance_elimination_plan and sk_problem_parameter_block_index have no reference counterpart)
 %include "skeres_amd.h"
 
 // load the native libraries as the reference's module class does (ceres.i:213-223)

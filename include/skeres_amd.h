@@ -334,6 +334,9 @@ double sk_problem_get_parameter_upper_bound(const sk_problem* p, const double* v
 int sk_problem_num_residual_blocks(const sk_problem* p);   /* Problem::NumResidualBlocks */
 int sk_problem_num_parameter_blocks(const sk_problem* p);  /* Problem::NumParameterBlocks */
 int sk_problem_num_parameters(const sk_problem* p);        /* Problem::NumParameters */
+/* (no reference counterpart) the index of a parameter block in the problem's own order — the order of first mention, which the
+ * *_of_block arrays of the plan functions below follow —, or -1 when values is no parameter block of the problem */
+int sk_problem_parameter_block_index(const sk_problem* p, const double* values);
 int sk_problem_num_residuals(const sk_problem* p);         /* Problem::NumResiduals */
 
 /* ---- Problem::Evaluate: ceres::Problem::Evaluate(EvaluateOptions, cost, residuals, gradient, CRSMatrix*) -----------------
@@ -404,7 +407,22 @@ int sk_problem_evaluate(sk_problem* p, const sk_evaluate_options* o, double* cos
  * the Jacobian is rank deficient (sk_last_error names the first offending block and coordinate, else the pivot ratio; getters
  * afterwards are SK_ERR_INVALID_ARGUMENT); SK_ERR_UNSUPPORTED — dense-row problems, a tangent size above 16, more than 32 768
  * columns (the dense matrix of (N + k, padded to blocks of 128)^2 doubles is a cap on memory; covariance at bundle-adjustment scale
- * through the reduced camera system is not built).  Host-callback blocks are taken; one device, no world of ranks. */
+ * takes the Schur elimination below).  Host-callback blocks are taken; one device, no world of ranks.
+ *   Schur elimination (sk_covariance_options_set_schur_elimination, off by default: then the route above, byte for byte).  With it
+ *              an independent set E of the moving blocks is eliminated block by block in front of the dense factorisation, and the
+ *              eliminated blocks are substituted back behind it: H = [[U, W], [W^T, V]], V block diagonal over E, H~ = D H D with D
+ *              over all columns, per e-block V~_e = L_e L_e^T and X_ge = D_g W_ge D_e L_e^-T, S~ = U~ - sum_e X_ge X_g'e^T factored
+ *              densely with the selection as its border.  E is greedy: two blocks are neighbours when a residual block stores both;
+ *              the moving blocks are visited in ascending order of (number of distinct neighbours, parameter-block index) and a
+ *              block joins E when none of its neighbours is in E yet; the rest, F, keeps the problem's order.  E depends on the
+ *              problem alone (bundle adjustment: the points; a block in no residual block joins first and is reported as above).
+ *              A requested e-block adds all its F-neighbours to the selection ("selected_columns" counts them).  Every problem
+ *              the dense route takes in kind is taken; SK_ERR_UNSUPPORTED from host data alone: dense rows, a tangent size above
+ *              16, more than 32 768 columns left AFTER the elimination, more than 2^31 - 1 Schur terms.  Two computes return the
+ *              same bytes; the two routes agree to rounding, not bitwise.
+ *   min_reciprocal_condition_number  is compared with min L_jj^2 / max L_jj^2 of the Cholesky factor of H~.  With the Schur
+ *              elimination that is the factor of H~ WITH E ORDERED FIRST (the pivots of every L_e and of S~'s factor), so the value
+ *              differs from the dense route's on the same problem; the rule and its messages are otherwise the same. */
 typedef struct sk_covariance_options sk_covariance_options;   /* ceres::Covariance::Options (ceres/covariance.h via ceres.i:29,141) */
 typedef struct sk_covariance sk_covariance;                   /* ceres::Covariance (ceres/covariance.h via ceres.i:29,141) */
 sk_covariance_options* sk_covariance_options_new(void);       /* apply_loss_function 1, min_reciprocal_condition_number 1e-14, current device */
@@ -412,6 +430,11 @@ void sk_covariance_options_free(sk_covariance_options* o);
 int sk_covariance_options_set_apply_loss_function(sk_covariance_options* o, int on);                  /* Covariance::Options::apply_loss_function */
 int sk_covariance_options_set_min_reciprocal_condition_number(sk_covariance_options* o, double v);    /* Covariance::Options::min_reciprocal_condition_number; [0, 1), not NaN */
 int sk_covariance_options_set_device(sk_covariance_options* o, int hip_device);                       /* (no reference counterpart) */
+int sk_covariance_options_set_schur_elimination(sk_covariance_options* o, int on);                    /* (no reference counterpart) default 0: see above */
+/* (no reference counterpart) the eliminated set of the Schur elimination, from host data alone (no device): eliminated_of_block
+ * [parameter blocks], may be NULL: 1 in E, 0 in F, -1 constant / no columns; the number of blocks in E, the columns of the reduced
+ * matrix and the number of Schur terms (any may be NULL).  SK_ERR_UNSUPPORTED as a compute with the option on. */
+int sk_covariance_elimination_plan(const sk_problem* p, int* eliminated_of_block, int* num_eliminated, int* reduced_columns, long long* schur_terms);
 sk_covariance* sk_covariance_new(const sk_covariance_options* o /* may be NULL */);                   /* Covariance::Covariance(options) */
 void sk_covariance_free(sk_covariance* c);
 /* Covariance::Compute(covariance_blocks, problem): the pairs (blocks1[i], blocks2[i]) */
@@ -423,8 +446,9 @@ int sk_covariance_get_block_in_tangent_space(const sk_covariance* c, const doubl
 int sk_covariance_get_matrix(const sk_covariance* c, double* const* blocks, int n, double* out);                        /* Covariance::GetCovarianceMatrix: (sum sizes)^2, listed order */
 int sk_covariance_get_matrix_in_tangent_space(const sk_covariance* c, double* const* blocks, int n, double* out);       /* Covariance::GetCovarianceMatrixInTangentSpace */
 /* (no reference counterpart) of the last compute: "columns" (N), "selected_columns" (k), "normal_matrix_pairs",
- * "reciprocal_pivot_ratio", "phase_seconds_0".."phase_seconds_4" — device seconds from HIP events: 0 evaluation, 1 assembly and
- * scaling, 2 factorisation, 3 extraction, 4 downloads.  SK_ERR_INVALID_ARGUMENT for another name or before a compute reached the device. */
+ * "reciprocal_pivot_ratio", "schur_elimination" (0 or 1), "eliminated_blocks", "reduced_columns" (N without the elimination),
+ * "schur_terms", "phase_seconds_0".."phase_seconds_4" — device seconds from HIP events: 0 evaluation, 1 assembly and
+ * scaling (with the elimination: up to and including the Schur update), 2 factorisation, 3 extraction, 4 downloads.  SK_ERR_INVALID_ARGUMENT for another name or before a compute reached the device. */
 int sk_covariance_stat(const sk_covariance* c, const char* name, double* value);
 /* (no reference counterpart) what a binding sizes its arrays by: the size and the tangent size of a parameter block of the problem
  * of the last successful compute (either pointer may be NULL).  SK_ERR_INVALID_ARGUMENT as for the getters. */

@@ -91,6 +91,7 @@ _SIGS = {
     "sk_problem_add_dense_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_void_p, _dp, C.c_int]),
     "sk_problem_num_residual_blocks": (C.c_int, [C.c_void_p]),
     "sk_problem_num_parameter_blocks": (C.c_int, [C.c_void_p]),
+    "sk_problem_parameter_block_index": (C.c_int, [C.c_void_p, _dp]),
     "sk_problem_num_parameters": (C.c_int, [C.c_void_p]),
     "sk_problem_num_residuals": (C.c_int, [C.c_void_p]),
     "sk_options_new": (C.c_void_p, []),
@@ -192,6 +193,8 @@ _SIGS = {
     "sk_covariance_options_set_apply_loss_function": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_covariance_options_set_min_reciprocal_condition_number": (C.c_int, [C.c_void_p, C.c_double]),
     "sk_covariance_options_set_device": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_covariance_options_set_schur_elimination": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_covariance_elimination_plan": (C.c_int, [C.c_void_p, _ip, _ip, _ip, C.POINTER(C.c_longlong)]),
     "sk_covariance_new": (C.c_void_p, [C.c_void_p]),
     "sk_covariance_free": (None, [C.c_void_p]),
     "sk_covariance_compute": (C.c_int, [C.c_void_p, C.c_void_p, _dpp, _dpp, C.c_int]),
@@ -1282,6 +1285,11 @@ class Problem:
     def numParameterBlocks(self):
         return lib().sk_problem_num_parameter_blocks(self._h)
 
+    def parameterBlockIndex(self, block):
+        """(no reference counterpart) the block's index in the problem's own order (first mention), which the *_of_block arrays
+        of the plan functions follow; -1 when it is no parameter block of the problem."""
+        return lib().sk_problem_parameter_block_index(self._h, block.cast())
+
     def numParameters(self):
         return lib().sk_problem_num_parameters(self._h)
 
@@ -1313,6 +1321,22 @@ class Covariance:
 
         def setDevice(self, device):
             _check_arg(lib().sk_covariance_options_set_device(self._h, int(device)))
+
+        def schurElimination(self, on):
+            """(no reference counterpart; default off) eliminate an independent set of blocks — in bundle adjustment the points —
+            in front of the dense factorisation: the route for problems of more than 32 768 columns (include/skeres_amd.h)."""
+            _check_arg(lib().sk_covariance_options_set_schur_elimination(self._h, int(bool(on))))
+
+    @staticmethod
+    def eliminationPlan(problem):
+        """The eliminated set of Options.schurElimination for this problem, from host data alone (sk_covariance_elimination_plan):
+        a dict with eliminated_of_block (per parameter block: 1 in E, 0 in F, -1 constant / no columns), num_eliminated,
+        reduced_columns and schur_terms."""
+        of_block = np.zeros(max(lib().sk_problem_num_parameter_blocks(problem._h), 1), dtype=np.int32)
+        n, cols, terms = C.c_int(), C.c_int(), C.c_longlong()
+        _check_arg(lib().sk_covariance_elimination_plan(problem._h, of_block.ctypes.data_as(_ip), C.byref(n), C.byref(cols), C.byref(terms)))
+        return dict(eliminated_of_block=of_block[:lib().sk_problem_num_parameter_blocks(problem._h)].copy(), num_eliminated=n.value,
+                    reduced_columns=cols.value, schur_terms=terms.value)
 
     def __init__(self, options=None):
         self._h = lib().sk_covariance_new(options._h if options is not None else None)

@@ -10,6 +10,7 @@
 #include "evaluate_kernels.hpp"
 #include "cgnr_plan.hpp"
 #include "covariance.hpp"
+#include "covariance_plan.hpp"
 #include "evaluate_plan.hpp"
 #include "solver.hpp"
 
@@ -665,6 +666,32 @@ int sk_covariance_options_set_min_reciprocal_condition_number(sk_covariance_opti
 int sk_covariance_options_set_device(sk_covariance_options* o, int dev) {
   if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
   o->o.device = dev; return SK_OK;
+}
+int sk_problem_parameter_block_index(const sk_problem* p, const double* values) {
+  if (!p) return -1;
+  auto it = p->p.block_of.find(const_cast<double*>(values));
+  return it == p->p.block_of.end() ? -1 : it->second;
+}
+int sk_covariance_options_set_schur_elimination(sk_covariance_options* o, int on) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.schur_elimination = on != 0; return SK_OK;
+}
+int sk_covariance_elimination_plan(const sk_problem* p, int* eliminated_of_block, int* num_eliminated, int* reduced_columns, long long* schur_terms) {
+  SK_GUARD_BEGIN
+  if (!p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  CovariancePlan plan;
+  std::string why;
+  const int rc = covariance_plan_build(p->p, {}, &plan, &why, /*schur*/ true);
+  if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
+  if (eliminated_of_block) {
+    for (size_t b = 0; b < p->p.block_ptr.size(); ++b) eliminated_of_block[b] = -1;
+    for (size_t c = 0; c < plan.cb_block.size(); ++c) eliminated_of_block[plan.cb_block[c]] = plan.cb_elim[c];
+  }
+  if (num_eliminated) *num_eliminated = plan.num_elim;
+  if (reduced_columns) *reduced_columns = plan.red_cols;
+  if (schur_terms) *schur_terms = plan.schur_terms;
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
 sk_covariance* sk_covariance_new(const sk_covariance_options* o) {
   SK_GUARD_BEGIN

@@ -3,7 +3,9 @@
 // H~ = D H D with the k selected columns as unit rows behind it, a PARTIAL factorisation of the bordered matrix by cholesky_factor
 // — H's block columns are factored, the border is left holding -Sel^T H~^-1 Sel, the selected block of the inverse, negated —,
 // the pivot ratio, the extraction of the requested blocks into one packed buffer, one download.  Everything runs on one stream,
-// launch by launch: no resident chain, no kernel that waits for another.
+// launch by launch: no resident chain, no kernel that waits for another.  With CovarianceOptions::schur_elimination an independent
+// set of column blocks is eliminated block by block in front of that factorisation and substituted back behind it (covariance_plan.hpp,
+// "Schur elimination"): the dense matrix is then the reduced one, S~ = U~ - sum_e X_ge X_g'e^T.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -59,14 +61,17 @@ struct Bordered {
     SK_HIP_TRY(hipStreamSynchronize(s));  // (`none` and `sc` go out of scope)
     return SK_OK;
   }
-  // steps 3 to 5; *zero: the first column with an exactly zero diagonal entry (INT_MAX: none — then the matrix was factored)
-  int scale_and_factor(hipStream_t s, int* zero, Marks* marks) {
+  // step 3; *zero: the first column with an exactly zero diagonal entry (INT_MAX: none)
+  int scale(hipStream_t s, int* zero, Marks* marks) {
     launch_cov_scale(S.p, ld, n, npad_h, d.p, zero_col.p, sel_col.p, k, s);
     SK_HIP_TRY(hipGetLastError());
     if (marks) marks->mark();
     SK_HIP_TRY(hipMemcpyAsync(zero, zero_col.p, sizeof(int), hipMemcpyDeviceToHost, s));
     SK_HIP_TRY(hipStreamSynchronize(s));
-    if (*zero != INT_MAX) return SK_OK;
+    return SK_OK;
+  }
+  // steps 4 and 5
+  int factor(hipStream_t s, Marks* marks) {
     SK_HIP_TRY(cholesky_init());
     cholesky_factor(S.p, ld, npad, Linv.p, info.p, kCovarianceGroup, s, /*ctx*/ nullptr, /*kt*/ nullptr, /*last*/ nullptr, /*allow_chain*/ false,
                     /*ncols*/ npad_h / 128, /*tail_rows*/ (npad - npad_h) / 128);
@@ -74,6 +79,11 @@ struct Bordered {
     SK_HIP_TRY(hipGetLastError());
     if (marks) marks->mark();
     return SK_OK;
+  }
+  // steps 3 to 5 (a zero diagonal entry: the matrix is not factored)
+  int scale_and_factor(hipStream_t s, int* zero, Marks* marks) {
+    const int rc = scale(s, zero, marks);
+    return rc != SK_OK || *zero != INT_MAX ? rc : factor(s, marks);
   }
 };
 }  // namespace
@@ -96,7 +106,8 @@ int Covariance::compute(const Problem& p, double* const* blocks1, double* const*
 int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pairs) {
   CovariancePlan C;
   std::string why;
-  int rc = covariance_plan_build(p, pairs, &C, &why);
+  const bool schur = opt_.schur_elimination;
+  int rc = covariance_plan_build(p, pairs, &C, &why, schur);
   if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return SK_ERR_NO_DEVICE; }
@@ -146,11 +157,34 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
   SK_HIP_TRY(d_x.upload(x, s)); SK_HIP_TRY(d_pblocks.upload(pblocks, s));
   SK_HIP_TRY(d_partial.alloc((size_t)std::max(C.num_partials, 1) * kCovarianceTile));
   SK_HIP_TRY(d_out.alloc((size_t)std::max<long>(C.out_size, 1))); SK_HIP_TRY(d_out.zero(s));
+  // Schur elimination: what the plan adds, the tiles, the diagonal over all columns, the pivots of the e-blocks
+  DevBuf<int> d_cb_red, d_cb_elim, d_pair_tile, d_pair_flip, d_e_cb, d_ew_begin, d_ew_tile, d_ew_g, d_ew_sel, d_sp_i, d_sp_j, d_st_a, d_st_b, d_st_ne, d_spart_pair,
+      d_spart_begin, d_spart_end, d_spart_out, d_slong_pair, d_slong_begin, d_req_ea, d_req_eb, d_zero, d_einfo;
+  DevBuf<double> d_tiles, d_all, d_slot, d_spartial;
+  const std::vector<int> no_zero(1, INT_MAX);
+  if (schur) {
+    SK_HIP_TRY(d_cb_red.upload(padded(C.cb_red), s)); SK_HIP_TRY(d_cb_elim.upload(padded(C.cb_elim), s));
+    SK_HIP_TRY(d_pair_tile.upload(padded(C.pair_tile), s)); SK_HIP_TRY(d_pair_flip.upload(padded(C.pair_flip), s));
+    SK_HIP_TRY(d_e_cb.upload(padded(C.e_cb), s)); SK_HIP_TRY(d_ew_begin.upload(C.ew_begin, s));
+    SK_HIP_TRY(d_ew_tile.upload(padded(C.ew_tile), s)); SK_HIP_TRY(d_ew_g.upload(padded(C.ew_g), s)); SK_HIP_TRY(d_ew_sel.upload(padded(C.ew_sel), s));
+    SK_HIP_TRY(d_sp_i.upload(padded(C.sp_i), s)); SK_HIP_TRY(d_sp_j.upload(padded(C.sp_j), s));
+    SK_HIP_TRY(d_st_a.upload(padded(C.st_a), s)); SK_HIP_TRY(d_st_b.upload(padded(C.st_b), s)); SK_HIP_TRY(d_st_ne.upload(padded(C.st_ne), s));
+    SK_HIP_TRY(d_spart_pair.upload(padded(C.spart_pair), s)); SK_HIP_TRY(d_spart_begin.upload(padded(C.spart_begin), s));
+    SK_HIP_TRY(d_spart_end.upload(padded(C.spart_end), s)); SK_HIP_TRY(d_spart_out.upload(padded(C.spart_out), s));
+    SK_HIP_TRY(d_slong_pair.upload(padded(C.slong_pair), s)); SK_HIP_TRY(d_slong_begin.upload(C.slong_begin, s));
+    SK_HIP_TRY(d_req_ea.upload(padded(C.req_ea), s)); SK_HIP_TRY(d_req_eb.upload(padded(C.req_eb), s));
+    SK_HIP_TRY(d_zero.upload(no_zero, s)); SK_HIP_TRY(d_einfo.alloc(1)); SK_HIP_TRY(d_einfo.zero(s));
+    SK_HIP_TRY(d_tiles.alloc((size_t)std::max(C.num_tiles, 1) * kCovarianceTile)); SK_HIP_TRY(d_tiles.zero(s));  // (an e-block that no residual block names keeps a zero tile)
+    SK_HIP_TRY(d_all.alloc((size_t)std::max(N, 1))); SK_HIP_TRY(d_slot.alloc((size_t)std::max(2 * C.num_elim, 1)));
+    SK_HIP_TRY(d_spartial.alloc((size_t)std::max(C.num_spartials, 1) * kCovarianceTile));
+  }
   SK_HIP_TRY(hipStreamSynchronize(s));  // (the padded copies above are temporaries)
 
   stats_.clear();
   stats_["columns"] = N; stats_["selected_columns"] = C.k; stats_["normal_matrix_pairs"] = (double)C.pair_i.size();
   stats_["reciprocal_pivot_ratio"] = 0.0;
+  stats_["schur_elimination"] = schur ? 1 : 0; stats_["eliminated_blocks"] = C.num_elim; stats_["reduced_columns"] = schur ? C.red_cols : N;
+  stats_["schur_terms"] = (double)C.schur_terms;
   double phase[kCovariancePhases] = {0, 0, 0, 0, 0};
   for (int i = 1; i <= 2; ++i) phase[0] += eval_seconds[i];  // (the evaluation launches and the finish: what produces the values array)
   auto keep_stats = [&] {
@@ -161,7 +195,7 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
   Marks marks; marks.s = s;
   marks.mark();
   Bordered B;
-  rc = B.alloc(N, C.sel_col, s);
+  rc = B.alloc(schur ? C.red_cols : N, C.sel_col, s);
   if (rc != SK_OK) return rc;
   // step 2: the normal matrix
   CovJac J{d_val.p, d_val_off.p, d_row_off.p, d_slot_owner.p, d_slot_pos.p};
@@ -170,13 +204,49 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
   P.part_pair = d_part_pair.p; P.part_begin = d_part_begin.p; P.part_end = d_part_end.p; P.part_out = d_part_out.p;
   P.long_pair = d_long_pair.p; P.long_begin = d_long_begin.p; P.pair_i = d_pair_i.p; P.pair_j = d_pair_j.p;
   P.term_si = d_term_si.p; P.term_sj = d_term_sj.p; P.cb_col = d_cb_col.p; P.cb_size = d_cb_size.p;
+  CovSchur Sc = {};
+  if (schur) {  // the (f, f') pairs go to the reduced matrix, the others to their tiles
+    P.cb_col = d_cb_red.p; P.pair_tile = d_pair_tile.p; P.pair_flip = d_pair_flip.p; P.tiles = d_tiles.p;
+    Sc.num_cb = (int)C.cb_col.size(); Sc.num_e = C.num_elim;
+    Sc.cb_col = d_cb_col.p; Sc.cb_red = d_cb_red.p; Sc.cb_size = d_cb_size.p; Sc.cb_elim = d_cb_elim.p; Sc.e_cb = d_e_cb.p;
+    Sc.ew_begin = d_ew_begin.p; Sc.ew_tile = d_ew_tile.p; Sc.ew_g = d_ew_g.p; Sc.ew_sel = d_ew_sel.p; Sc.tiles = d_tiles.p;
+    Sc.num_parts = (int)C.spart_pair.size(); Sc.num_long = (int)C.slong_pair.size();
+    Sc.part_pair = d_spart_pair.p; Sc.part_begin = d_spart_begin.p; Sc.part_end = d_spart_end.p; Sc.part_out = d_spart_out.p;
+    Sc.long_pair = d_slong_pair.p; Sc.long_begin = d_slong_begin.p; Sc.pair_i = d_sp_i.p; Sc.pair_j = d_sp_j.p;
+    Sc.term_a = d_st_a.p; Sc.term_b = d_st_b.p; Sc.term_ne = d_st_ne.p; Sc.req_ea = d_req_ea.p; Sc.req_eb = d_req_eb.p;
+  }
   launch_cov_normal_assemble(J, P, B.S.p, B.ld, d_partial.p, s);
   // steps 3 to 5
   int zero = INT_MAX;
-  rc = B.scale_and_factor(s, &zero, &marks);
-  if (rc != SK_OK) return rc;
-  phase[1] = marks.seconds(0);
+  if (!schur) {
+    rc = B.scale_and_factor(s, &zero, &marks);
+    if (rc != SK_OK) return rc;
+  } else {
+    // d over all columns first: the e-blocks need it before U is scaled, and a zero entry ends the compute here
+    launch_cov_schur_diag(Sc, B.S.p, B.ld, d_all.p, d_zero.p, s);
+    SK_HIP_TRY(hipGetLastError());
+    SK_HIP_TRY(hipMemcpyAsync(&zero, d_zero.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipStreamSynchronize(s));
+    if (zero == INT_MAX) {
+      launch_cov_schur_eblocks(Sc, d_all.p, d_slot.p, d_einfo.p, s);
+      int zero_f = INT_MAX;  // (no zero among the F columns: d_all covers them)
+      rc = B.scale(s, &zero_f, nullptr);
+      if (rc != SK_OK) return rc;
+      launch_cov_schur_update(Sc, B.S.p, B.ld, d_spartial.p, s);
+      SK_HIP_TRY(hipGetLastError());
+      marks.mark();
+      rc = B.factor(s, nullptr);
+      if (rc != SK_OK) return rc;
+      launch_cov_schur_pivot_ratio(d_slot.p, C.num_elim, B.ratio.p, s);
+      SK_HIP_TRY(hipGetLastError());
+      marks.mark();
+    } else {
+      marks.mark();
+    }
+  }
   if (zero != INT_MAX) {
+    SK_HIP_TRY(hipStreamSynchronize(s));
+    phase[1] = marks.seconds(0);
     int cb = 0;
     while (cb + 1 < (int)C.cb_col.size() && C.cb_col[cb + 1] <= zero) ++cb;
     keep_stats();
@@ -188,22 +258,24 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
   CovRequests R;
   R.num = (int)C.req_a.size(); R.ra = d_ra.p; R.rb = d_rb.p; R.a = d_a.p; R.b = d_b.p; R.tan_off = d_tan_off.p; R.amb_off = d_amb_off.p;
   R.pblocks = d_pblocks.p; R.x = d_x.p;
-  launch_cov_extract(R, B.border(), B.ld, B.d.p, d_out.p, s);
+  if (schur) launch_cov_schur_extract(R, Sc, B.border(), B.ld, d_all.p, d_out.p, s);
+  else launch_cov_extract(R, B.border(), B.ld, B.d.p, d_out.p, s);
   SK_HIP_TRY(hipGetLastError());
   marks.mark();
   std::vector<double> out((size_t)std::max<long>(C.out_size, 1));
   double ratio[2] = {0, 0};
-  int info = 0;
+  int info = 0, einfo = 0;
+  if (schur) SK_HIP_TRY(hipMemcpyAsync(&einfo, d_einfo.p, sizeof(int), hipMemcpyDeviceToHost, s));
   SK_HIP_TRY(hipMemcpyAsync(out.data(), d_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   SK_HIP_TRY(hipMemcpyAsync(ratio, B.ratio.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
   SK_HIP_TRY(hipMemcpyAsync(&info, B.info.p, sizeof(int), hipMemcpyDeviceToHost, s));
   marks.mark();
   SK_HIP_TRY(hipStreamSynchronize(s));
-  phase[2] = marks.seconds(1); phase[3] = marks.seconds(2); phase[4] = marks.seconds(3);
+  phase[1] = marks.seconds(0); phase[2] = marks.seconds(1); phase[3] = marks.seconds(2); phase[4] = marks.seconds(3);
   const double rcond = N == 0 ? 1.0 : ratio[1] > 0.0 && std::isfinite(ratio[0]) && std::isfinite(ratio[1]) ? ratio[0] / ratio[1] : 0.0;  // (N == 0: every block is constant)
   stats_["reciprocal_pivot_ratio"] = rcond;
   keep_stats();
-  if (info != 0 || (N > 0 && (!(ratio[0] > 0.0) || !std::isfinite(ratio[1])))) {
+  if (info != 0 || einfo != 0 || (N > 0 && (!(ratio[0] > 0.0) || !std::isfinite(ratio[1])))) {
     set_error("Covariance: the Jacobian is rank deficient: the factorisation of J^T J met a pivot that is not positive");
     return SK_ERR_EVALUATION_FAILED;
   }

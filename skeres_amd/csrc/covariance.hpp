@@ -15,6 +15,7 @@ struct CovarianceOptions {  // ceres::Covariance::Options (algorithm_type, null_
   bool apply_loss_function = true;
   double min_reciprocal_condition_number = 1e-14;
   int device = -1;  // -1: the current device
+  bool schur_elimination = false;  // (no reference counterpart) eliminate an independent set of blocks in front of the factorisation: covariance_plan.hpp
 };
 
 constexpr int kCovariancePhases = 5;  // 0 evaluation, 1 assembly and scaling, 2 factorisation, 3 extraction, 4 downloads

@@ -11,6 +11,20 @@
 //
 // Selection.  The distinct moving column blocks named by the requested pairs, in order of first appearance; their k columns are
 // the unit rows of the border behind H, and every requested pair knows where its block sits in the k x k result.
+//
+// Schur elimination (sk_covariance_options_set_schur_elimination; off by default, and then nothing below exists in the plan).
+// The eliminated set E is a greedy independent set over the moving column blocks, two of which are NEIGHBOURS when a residual
+// block stores both: the blocks are visited in ascending order of (number of distinct neighbours, parameter-block index), and a
+// block joins E when none of its neighbours is in E yet; F is the rest, in problem order.  (Bundle adjustment: the points, and
+// every camera stays in F because it neighbours a point of low degree; a chain: alternating blocks, the hub in F; a block that no
+// residual block names has degree 0 and joins E first.)  E depends on the problem alone.  With H = [[U, W], [W^T, V]], V block
+// diagonal over E, the pairs, terms and parts above stay as they are and are ROUTED: an (e, e) or (f, e) pair sums into a TILE of
+// kCovarianceTile doubles (tile t < |E|: V_e of the t-th e-block, later L_e; tile |E| + t: L_e^-1; then one tile per (f, e) pair,
+// rows of f by columns of e whichever of the two has the lower column), an (f, f') pair into the dense matrix, now n_F wide.
+// SCHUR TERMS: for every pair of F blocks (g >= g' by first column, g == g' included) that share an e-block, (tile of (g, e), tile
+// of (g', e)) per shared e in ascending order of e, cut into parts of 64 with the same long-pair mechanism.  A (g, e) tile is the
+// sum over all residual blocks on that pair.  F(e): the F-neighbours of e in ascending column order.  The selection is the requested
+// F blocks and, for every requested e, all of F(e); sel_col holds columns of the reduced matrix.
 #pragma once
 #include <string>
 #include <utility>
@@ -52,12 +66,29 @@ struct CovariancePlan {
   std::vector<int> req_ra, req_rb;            // first row / column inside the k x k result (-1: a constant block, the covariance is zero)
   std::vector<long> req_tan_off, req_amb_off; // first entry of the tangent (tangent(a) x tangent(b)) and ambient (size(a) x size(b)) block in the packed output
   long out_size = 0;
+  // Schur elimination (empty / 0 unless the plan was built with it)
+  bool schur = false;
+  std::vector<int> cb_elim;   // per column block: 1 in E, 0 in F
+  std::vector<int> cb_red;    // per column block: in F its first column of the reduced matrix, in E its index among the e-blocks
+  int num_elim = 0, red_cols = 0, num_tiles = 0;
+  long long schur_terms = 0;
+  std::vector<int> pair_tile, pair_flip;      // per pair: its tile (-1: the dense matrix); 1: the pair's i is the e-block, the tile is stored transposed
+  std::vector<int> e_cb;                      // the e-blocks (column blocks), ascending
+  std::vector<int> ew_begin;                  // [e-blocks + 1] F(e) as ranges of the three lists below
+  std::vector<int> ew_tile, ew_g, ew_sel;     // the (g, e) tile, the F column block g, g's first row among the k selected ones (-1: e was not requested)
+  std::vector<int> sp_i, sp_j, sp_begin;      // pairs of F blocks with Schur terms; [pairs + 1] into st_*
+  std::vector<int> st_a, st_b, st_ne;         // tile of (g, e), tile of (g', e), tangent size of e
+  std::vector<int> spart_pair, spart_begin, spart_end, spart_out, slong_pair, slong_begin;  // as part_* / long_* above
+  int num_spartials = 0;
+  std::vector<int> req_ea, req_eb;            // per requested pair: the e-block index of a / b (-1: in F, req_ra / req_rb hold its rows)
 };
 
 // "" when the covariance of this problem can be computed, else why not (SK_ERR_UNSUPPORTED): dense rows, a tangent size (or the
-// size of a parameterized block) above kCovarianceMaxBlock, more than kCovarianceMaxColumns columns.  Host data alone.
-std::string covariance_refusal(const Problem& p);
-// pairs: parameter blocks of the problem (indices), as requested.  Returns an sk_status; *why says what is wrong.
-int covariance_plan_build(const Problem& p, const std::vector<std::pair<int, int>>& pairs, CovariancePlan* plan, std::string* why);
+// size of a parameterized block) above kCovarianceMaxBlock, more than kCovarianceMaxColumns columns (schur: not checked here — the
+// plan counts the columns that are left after the elimination).  Host data alone.
+std::string covariance_refusal(const Problem& p, bool schur = false);
+// pairs: parameter blocks of the problem (indices), as requested.  Returns an sk_status; *why says what is wrong.  schur: with the
+// elimination (SK_ERR_UNSUPPORTED for more than kCovarianceMaxColumns reduced columns or more than INT_MAX Schur terms).
+int covariance_plan_build(const Problem& p, const std::vector<std::pair<int, int>>& pairs, CovariancePlan* plan, std::string* why, bool schur = false);
 
 }  // namespace sk
