@@ -208,7 +208,7 @@ int sk_loss_evaluate(const sk_loss_function* loss, const double* sq_norm, int n,
   std::vector<LossNode> nodes;
   if (loss) nodes = loss->l.nodes;
   const int root = nodes.empty() ? -1 : (int)nodes.size() - 1;
-  if (nodes.empty()) { LossNode t; t.type = kLossTrivial; t.f = t.g = -1; t.depth = 0; t.a = t.b = 0.0; nodes.push_back(t); }
+  nodes = loss_nodes_or_trivial(std::move(nodes));
   SK_HIP_TRY(dn.upload(nodes, nullptr));
   SK_HIP_TRY(ds.upload(std::vector<double>(sq_norm, sq_norm + n), nullptr));
   SK_HIP_TRY(dr.alloc(3 * (size_t)n));
@@ -685,7 +685,7 @@ int sk_covariance_elimination_plan(const sk_problem* p, int* eliminated_of_block
   if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
   if (eliminated_of_block) {
     for (size_t b = 0; b < p->p.block_ptr.size(); ++b) eliminated_of_block[b] = -1;
-    for (size_t c = 0; c < plan.cb_block.size(); ++c) eliminated_of_block[plan.cb_block[c]] = plan.cb_elim[c];
+    for (size_t c = 0; c < plan.cols.cb_block.size(); ++c) eliminated_of_block[plan.cols.cb_block[c]] = plan.cb_elim[c];
   }
   if (num_eliminated) *num_eliminated = plan.num_elim;
   if (reduced_columns) *reduced_columns = plan.red_cols;

@@ -63,6 +63,12 @@ struct DevBuf {
   hipError_t zero(hipStream_t s) { return n ? hipMemsetAsync(p, 0, n * sizeof(T), s) : hipSuccess; }
 };
 
+// The loss nodes as a kernel takes them: a problem without any gets one trivial node, so that the pointer is never null.
+inline std::vector<LossNode> loss_nodes_or_trivial(std::vector<LossNode> nodes) {
+  if (nodes.empty()) { LossNode t; t.type = kLossTrivial; t.f = t.g = -1; t.depth = 0; t.a = t.b = 0.0; nodes.push_back(t); }
+  return nodes;
+}
+
 struct Options {  // Solver.Options; Ceres 1.x defaults
   int linear_solver_type = SK_DENSE_QR;  // ceres default is SPARSE_NORMAL_CHOLESKY when built with a sparse backend, else DENSE_QR
   int linear_solver_type_given = -1;     // set when the solver in use is an alternate for the one asked for (capi.hip: make_solver)

@@ -15,26 +15,11 @@
 #include "covariance_kernels.hpp"
 #include "covariance_plan.hpp"
 #include "evaluate_kernels.hpp"
+#include "jacobian_device.hpp"
 
 namespace sk {
 
 namespace {
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-};
-// device time between marks on the stream, as sk_evaluate_options_set_launch_timing does it
-struct Marks {
-  hipStream_t s = nullptr;
-  std::vector<hipEvent_t> ev;
-  void mark() { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); ev.push_back(e); } }
-  double seconds(size_t i) const {
-    float ms = 0.f;
-    return i + 1 < ev.size() && hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess ? 1e-3 * ms : 0.0;
-  }
-  ~Marks() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-};
-
 constexpr int kCovarianceGroup = 3;  // SYRK depth of a full factorisation in 128-column blocks (Options::cholesky_group's automatic choice)
 
 // The bordered matrix of steps 3 to 5: H (n columns, padded to npad_h) and the k border rows behind it.
@@ -56,9 +41,8 @@ struct Bordered {
     SK_HIP_TRY(info.alloc(1)); SK_HIP_TRY(info.zero(s));
     const std::vector<int> none(1, INT_MAX);
     SK_HIP_TRY(zero_col.upload(none, s));
-    std::vector<int> sc = sel; if (sc.empty()) sc.push_back(0);
-    SK_HIP_TRY(sel_col.upload(sc, s));
-    SK_HIP_TRY(hipStreamSynchronize(s));  // (`none` and `sc` go out of scope)
+    SK_HIP_TRY(upload_padded(sel_col, sel, s));
+    SK_HIP_TRY(hipStreamSynchronize(s));  // (`none` goes out of scope)
     return SK_OK;
   }
   // step 3; *zero: the first column with an exactly zero diagonal entry (INT_MAX: none)
@@ -113,49 +97,46 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return SK_ERR_NO_DEVICE; }
   if (opt_.device >= 0) SK_HIP_TRY(hipSetDevice(opt_.device));
   const EvaluatePlan& E = C.eval;
-  const int num_pb = (int)p.block_ptr.size(), N = C.num_cols;
+  const TangentColumns& T = C.cols;
+  const PartList& parts = C.pair_parts;
+  const PartList& sparts = C.schur_parts;
+  const int num_pb = (int)p.block_ptr.size(), N = T.num_cols;
 
-  // step 1: the evaluation, by Problem::Evaluate's own code; the values array stays where it is
-  EvaluateOptions eo;
-  eo.apply_loss_function = opt_.apply_loss_function; eo.device = opt_.device;
-  double eval_seconds[kEvaluatePhases] = {0, 0, 0, 0, 0, 0};
-  DevBuf<double> d_val;
-  rc = problem_evaluate(p, &eo, nullptr, nullptr, nullptr, nullptr, eval_seconds, &d_val);
-  if (rc != SK_OK) return rc;
-
-  // the point (for the Plus-Jacobians of the lift) and the parameter blocks as the extraction reads them
-  std::vector<double> x((size_t)std::max(C.block_off[num_pb], 1), 0.0);
-  std::vector<ParamBlock> pblocks((size_t)std::max(num_pb, 1));
-  for (int b = 0; b < num_pb; ++b) {
-    std::memcpy(&x[C.block_off[b]], p.block_ptr[b], p.block_size[b] * sizeof(double));
-    ParamBlock& pb = pblocks[b];
-    pb.type = C.pb_type[b]; pb.global_size = C.pb_size[b]; pb.local_size = C.pb_local_size[b];
-    pb.constant_mask = C.pb_mask[b]; pb.global_off = C.block_off[b]; pb.local_off = C.pb_local_off[b];
-  }
-  auto padded = [](std::vector<int> v) { if (v.empty()) v.push_back(0); return v; };
-  auto padded_l = [](std::vector<long> v) { if (v.empty()) v.push_back(0); return v; };
-
+  // step 1: the evaluation, by Problem::Evaluate's own code (jacobian_device.hpp); the values array, the point (for the
+  // Plus-Jacobians of the lift) and the parameter blocks stay on the device, where the assembly and the extraction read them
   StreamGuard sg;
   SK_HIP_TRY(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
   hipStream_t s = sg.s;
-  DevBuf<int> d_val_off, d_row_off, d_slot_owner, d_slot_pos, d_part_pair, d_part_begin, d_part_end, d_part_out, d_long_pair, d_long_begin, d_pair_i, d_pair_j,
-      d_term_si, d_term_sj, d_cb_col, d_cb_size, d_ra, d_rb, d_a, d_b;
+  DeviceJacobian dj;
+  dj.gather(p, E, param_blocks(p, E, &T), opt_.apply_loss_function);
+  rc = dj.upload(/*want_values*/ true, /*by_column*/ true, s);
+  if (rc != SK_OK) return rc;
+  DevBuf<double> d_res, d_cterm;
+  SK_HIP_TRY(d_res.alloc((size_t)std::max(E.num_rows, 1))); SK_HIP_TRY(d_cterm.alloc(std::max<size_t>(E.blocks.size(), 1)));
+  Marks eval_marks; eval_marks.s = s;
+  eval_marks.mark();
+  rc = dj.evaluate(dj.x(), true);
+  if (rc != SK_OK) return rc;
+  SK_HIP_TRY(hipGetLastError());
+  dj.finish(dj.x(), d_res.p, dj.values(), d_cterm.p);
+  eval_marks.mark();
+  int failed = 0;
+  SK_HIP_TRY(hipMemcpyAsync(&failed, dj.fail_flag(), sizeof(int), hipMemcpyDeviceToHost, s));
+
+  DevBuf<int> d_part_pair, d_part_begin, d_part_end, d_part_out, d_long_pair, d_long_begin, d_pair_i, d_pair_j, d_term_si, d_term_sj, d_cb_col, d_cb_size, d_ra, d_rb,
+      d_a, d_b;
   DevBuf<long> d_tan_off, d_amb_off;
-  DevBuf<double> d_x, d_partial, d_out;
-  DevBuf<ParamBlock> d_pblocks;
-  SK_HIP_TRY(d_val_off.upload(E.val_off, s)); SK_HIP_TRY(d_row_off.upload(E.row_off, s));
-  SK_HIP_TRY(d_slot_owner.upload(padded(E.slot_owner), s)); SK_HIP_TRY(d_slot_pos.upload(padded(E.slot_pos), s));
-  SK_HIP_TRY(d_part_pair.upload(padded(C.part_pair), s)); SK_HIP_TRY(d_part_begin.upload(padded(C.part_begin), s));
-  SK_HIP_TRY(d_part_end.upload(padded(C.part_end), s)); SK_HIP_TRY(d_part_out.upload(padded(C.part_out), s));
-  SK_HIP_TRY(d_long_pair.upload(padded(C.long_pair), s)); SK_HIP_TRY(d_long_begin.upload(C.long_begin, s));
-  SK_HIP_TRY(d_pair_i.upload(padded(C.pair_i), s)); SK_HIP_TRY(d_pair_j.upload(padded(C.pair_j), s));
-  SK_HIP_TRY(d_term_si.upload(padded(C.term_si), s)); SK_HIP_TRY(d_term_sj.upload(padded(C.term_sj), s));
-  SK_HIP_TRY(d_cb_col.upload(padded(C.cb_col), s)); SK_HIP_TRY(d_cb_size.upload(padded(C.cb_size), s));
-  SK_HIP_TRY(d_ra.upload(padded(C.req_ra), s)); SK_HIP_TRY(d_rb.upload(padded(C.req_rb), s));
-  SK_HIP_TRY(d_a.upload(padded(C.req_a), s)); SK_HIP_TRY(d_b.upload(padded(C.req_b), s));
-  SK_HIP_TRY(d_tan_off.upload(padded_l(C.req_tan_off), s)); SK_HIP_TRY(d_amb_off.upload(padded_l(C.req_amb_off), s));
-  SK_HIP_TRY(d_x.upload(x, s)); SK_HIP_TRY(d_pblocks.upload(pblocks, s));
-  SK_HIP_TRY(d_partial.alloc((size_t)std::max(C.num_partials, 1) * kCovarianceTile));
+  DevBuf<double> d_partial, d_out;
+  SK_HIP_TRY(upload_padded(d_part_pair, parts.owner, s)); SK_HIP_TRY(upload_padded(d_part_begin, parts.begin, s));
+  SK_HIP_TRY(upload_padded(d_part_end, parts.end, s)); SK_HIP_TRY(upload_padded(d_part_out, parts.out, s));
+  SK_HIP_TRY(upload_padded(d_long_pair, parts.long_owner, s)); SK_HIP_TRY(d_long_begin.upload(parts.long_begin, s));
+  SK_HIP_TRY(upload_padded(d_pair_i, C.pair_i, s)); SK_HIP_TRY(upload_padded(d_pair_j, C.pair_j, s));
+  SK_HIP_TRY(upload_padded(d_term_si, C.term_si, s)); SK_HIP_TRY(upload_padded(d_term_sj, C.term_sj, s));
+  SK_HIP_TRY(upload_padded(d_cb_col, T.cb_col, s)); SK_HIP_TRY(upload_padded(d_cb_size, T.cb_size, s));
+  SK_HIP_TRY(upload_padded(d_ra, C.req_ra, s)); SK_HIP_TRY(upload_padded(d_rb, C.req_rb, s));
+  SK_HIP_TRY(upload_padded(d_a, C.req_a, s)); SK_HIP_TRY(upload_padded(d_b, C.req_b, s));
+  SK_HIP_TRY(upload_padded(d_tan_off, C.req_tan_off, s)); SK_HIP_TRY(upload_padded(d_amb_off, C.req_amb_off, s));
+  SK_HIP_TRY(d_partial.alloc((size_t)std::max(parts.num_partials, 1) * kCovarianceTile));
   SK_HIP_TRY(d_out.alloc((size_t)std::max<long>(C.out_size, 1))); SK_HIP_TRY(d_out.zero(s));
   // Schur elimination: what the plan adds, the tiles, the diagonal over all columns, the pivots of the e-blocks
   DevBuf<int> d_cb_red, d_cb_elim, d_pair_tile, d_pair_flip, d_e_cb, d_ew_begin, d_ew_tile, d_ew_g, d_ew_sel, d_sp_i, d_sp_j, d_st_a, d_st_b, d_st_ne, d_spart_pair,
@@ -163,22 +144,23 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
   DevBuf<double> d_tiles, d_all, d_slot, d_spartial;
   const std::vector<int> no_zero(1, INT_MAX);
   if (schur) {
-    SK_HIP_TRY(d_cb_red.upload(padded(C.cb_red), s)); SK_HIP_TRY(d_cb_elim.upload(padded(C.cb_elim), s));
-    SK_HIP_TRY(d_pair_tile.upload(padded(C.pair_tile), s)); SK_HIP_TRY(d_pair_flip.upload(padded(C.pair_flip), s));
-    SK_HIP_TRY(d_e_cb.upload(padded(C.e_cb), s)); SK_HIP_TRY(d_ew_begin.upload(C.ew_begin, s));
-    SK_HIP_TRY(d_ew_tile.upload(padded(C.ew_tile), s)); SK_HIP_TRY(d_ew_g.upload(padded(C.ew_g), s)); SK_HIP_TRY(d_ew_sel.upload(padded(C.ew_sel), s));
-    SK_HIP_TRY(d_sp_i.upload(padded(C.sp_i), s)); SK_HIP_TRY(d_sp_j.upload(padded(C.sp_j), s));
-    SK_HIP_TRY(d_st_a.upload(padded(C.st_a), s)); SK_HIP_TRY(d_st_b.upload(padded(C.st_b), s)); SK_HIP_TRY(d_st_ne.upload(padded(C.st_ne), s));
-    SK_HIP_TRY(d_spart_pair.upload(padded(C.spart_pair), s)); SK_HIP_TRY(d_spart_begin.upload(padded(C.spart_begin), s));
-    SK_HIP_TRY(d_spart_end.upload(padded(C.spart_end), s)); SK_HIP_TRY(d_spart_out.upload(padded(C.spart_out), s));
-    SK_HIP_TRY(d_slong_pair.upload(padded(C.slong_pair), s)); SK_HIP_TRY(d_slong_begin.upload(C.slong_begin, s));
-    SK_HIP_TRY(d_req_ea.upload(padded(C.req_ea), s)); SK_HIP_TRY(d_req_eb.upload(padded(C.req_eb), s));
+    SK_HIP_TRY(upload_padded(d_cb_red, C.cb_red, s)); SK_HIP_TRY(upload_padded(d_cb_elim, C.cb_elim, s));
+    SK_HIP_TRY(upload_padded(d_pair_tile, C.pair_tile, s)); SK_HIP_TRY(upload_padded(d_pair_flip, C.pair_flip, s));
+    SK_HIP_TRY(upload_padded(d_e_cb, C.e_cb, s)); SK_HIP_TRY(d_ew_begin.upload(C.ew_begin, s));
+    SK_HIP_TRY(upload_padded(d_ew_tile, C.ew_tile, s)); SK_HIP_TRY(upload_padded(d_ew_g, C.ew_g, s)); SK_HIP_TRY(upload_padded(d_ew_sel, C.ew_sel, s));
+    SK_HIP_TRY(upload_padded(d_sp_i, C.sp_i, s)); SK_HIP_TRY(upload_padded(d_sp_j, C.sp_j, s));
+    SK_HIP_TRY(upload_padded(d_st_a, C.st_a, s)); SK_HIP_TRY(upload_padded(d_st_b, C.st_b, s)); SK_HIP_TRY(upload_padded(d_st_ne, C.st_ne, s));
+    SK_HIP_TRY(upload_padded(d_spart_pair, sparts.owner, s)); SK_HIP_TRY(upload_padded(d_spart_begin, sparts.begin, s));
+    SK_HIP_TRY(upload_padded(d_spart_end, sparts.end, s)); SK_HIP_TRY(upload_padded(d_spart_out, sparts.out, s));
+    SK_HIP_TRY(upload_padded(d_slong_pair, sparts.long_owner, s)); SK_HIP_TRY(d_slong_begin.upload(sparts.long_begin, s));
+    SK_HIP_TRY(upload_padded(d_req_ea, C.req_ea, s)); SK_HIP_TRY(upload_padded(d_req_eb, C.req_eb, s));
     SK_HIP_TRY(d_zero.upload(no_zero, s)); SK_HIP_TRY(d_einfo.alloc(1)); SK_HIP_TRY(d_einfo.zero(s));
     SK_HIP_TRY(d_tiles.alloc((size_t)std::max(C.num_tiles, 1) * kCovarianceTile)); SK_HIP_TRY(d_tiles.zero(s));  // (an e-block that no residual block names keeps a zero tile)
     SK_HIP_TRY(d_all.alloc((size_t)std::max(N, 1))); SK_HIP_TRY(d_slot.alloc((size_t)std::max(2 * C.num_elim, 1)));
-    SK_HIP_TRY(d_spartial.alloc((size_t)std::max(C.num_spartials, 1) * kCovarianceTile));
+    SK_HIP_TRY(d_spartial.alloc((size_t)std::max(sparts.num_partials, 1) * kCovarianceTile));
   }
-  SK_HIP_TRY(hipStreamSynchronize(s));  // (the padded copies above are temporaries)
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  if (failed) { set_error("Evaluate: a cost functor reported failure"); return SK_ERR_EVALUATION_FAILED; }
 
   stats_.clear();
   stats_["columns"] = N; stats_["selected_columns"] = C.k; stats_["normal_matrix_pairs"] = (double)C.pair_i.size();
@@ -186,7 +168,7 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
   stats_["schur_elimination"] = schur ? 1 : 0; stats_["eliminated_blocks"] = C.num_elim; stats_["reduced_columns"] = schur ? C.red_cols : N;
   stats_["schur_terms"] = (double)C.schur_terms;
   double phase[kCovariancePhases] = {0, 0, 0, 0, 0};
-  for (int i = 1; i <= 2; ++i) phase[0] += eval_seconds[i];  // (the evaluation launches and the finish: what produces the values array)
+  phase[0] = eval_marks.seconds(0);  // (the evaluation launches and the finish: what produces the values array)
   auto keep_stats = [&] {
     for (int i = 0; i < kCovariancePhases; ++i) stats_["phase_seconds_" + std::to_string(i)] = phase[i];
     has_stats_ = true;
@@ -198,19 +180,19 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
   rc = B.alloc(schur ? C.red_cols : N, C.sel_col, s);
   if (rc != SK_OK) return rc;
   // step 2: the normal matrix
-  CovJac J{d_val.p, d_val_off.p, d_row_off.p, d_slot_owner.p, d_slot_pos.p};
+  CovJac J{dj.values(), dj.val_off(), dj.row_off(), dj.slot_owner(), dj.slot_pos()};
   CovPairs P;
-  P.num_parts = (int)C.part_pair.size(); P.num_long = (int)C.long_pair.size();
+  P.num_parts = (int)parts.owner.size(); P.num_long = (int)parts.long_owner.size();
   P.part_pair = d_part_pair.p; P.part_begin = d_part_begin.p; P.part_end = d_part_end.p; P.part_out = d_part_out.p;
   P.long_pair = d_long_pair.p; P.long_begin = d_long_begin.p; P.pair_i = d_pair_i.p; P.pair_j = d_pair_j.p;
   P.term_si = d_term_si.p; P.term_sj = d_term_sj.p; P.cb_col = d_cb_col.p; P.cb_size = d_cb_size.p;
   CovSchur Sc = {};
   if (schur) {  // the (f, f') pairs go to the reduced matrix, the others to their tiles
     P.cb_col = d_cb_red.p; P.pair_tile = d_pair_tile.p; P.pair_flip = d_pair_flip.p; P.tiles = d_tiles.p;
-    Sc.num_cb = (int)C.cb_col.size(); Sc.num_e = C.num_elim;
+    Sc.num_cb = (int)T.cb_col.size(); Sc.num_e = C.num_elim;
     Sc.cb_col = d_cb_col.p; Sc.cb_red = d_cb_red.p; Sc.cb_size = d_cb_size.p; Sc.cb_elim = d_cb_elim.p; Sc.e_cb = d_e_cb.p;
     Sc.ew_begin = d_ew_begin.p; Sc.ew_tile = d_ew_tile.p; Sc.ew_g = d_ew_g.p; Sc.ew_sel = d_ew_sel.p; Sc.tiles = d_tiles.p;
-    Sc.num_parts = (int)C.spart_pair.size(); Sc.num_long = (int)C.slong_pair.size();
+    Sc.num_parts = (int)sparts.owner.size(); Sc.num_long = (int)sparts.long_owner.size();
     Sc.part_pair = d_spart_pair.p; Sc.part_begin = d_spart_begin.p; Sc.part_end = d_spart_end.p; Sc.part_out = d_spart_out.p;
     Sc.long_pair = d_slong_pair.p; Sc.long_begin = d_slong_begin.p; Sc.pair_i = d_sp_i.p; Sc.pair_j = d_sp_j.p;
     Sc.term_a = d_st_a.p; Sc.term_b = d_st_b.p; Sc.term_ne = d_st_ne.p; Sc.req_ea = d_req_ea.p; Sc.req_eb = d_req_eb.p;
@@ -248,16 +230,16 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
     SK_HIP_TRY(hipStreamSynchronize(s));
     phase[1] = marks.seconds(0);
     int cb = 0;
-    while (cb + 1 < (int)C.cb_col.size() && C.cb_col[cb + 1] <= zero) ++cb;
+    while (cb + 1 < (int)T.cb_col.size() && T.cb_col[cb + 1] <= zero) ++cb;
     keep_stats();
     set_error("Covariance: the Jacobian is rank deficient: column %d (parameter block %d, coordinate %d of its tangent space) is zero — no residual block depends on it",
-              zero, C.cb_block[cb], zero - C.cb_col[cb]);
+              zero, T.cb_block[cb], zero - T.cb_col[cb]);
     return SK_ERR_EVALUATION_FAILED;
   }
   // step 6: the requested blocks, one packed buffer, one download
   CovRequests R;
   R.num = (int)C.req_a.size(); R.ra = d_ra.p; R.rb = d_rb.p; R.a = d_a.p; R.b = d_b.p; R.tan_off = d_tan_off.p; R.amb_off = d_amb_off.p;
-  R.pblocks = d_pblocks.p; R.x = d_x.p;
+  R.pblocks = dj.pblocks(); R.x = dj.x();
   if (schur) launch_cov_schur_extract(R, Sc, B.border(), B.ld, d_all.p, d_out.p, s);
   else launch_cov_extract(R, B.border(), B.ld, B.d.p, d_out.p, s);
   SK_HIP_TRY(hipGetLastError());
@@ -287,7 +269,7 @@ int Covariance::run(const Problem& p, const std::vector<std::pair<int, int>>& pa
 
   block_of_.clear();
   for (int b = 0; b < num_pb; ++b) block_of_[p.block_ptr[b]] = b;
-  size_ = C.pb_size; tangent_ = C.pb_local_size;
+  size_ = T.pb_size; tangent_ = T.pb_local_size;
   req_of_.clear();
   for (size_t r = 0; r < C.req_a.size(); ++r) req_of_[{C.req_a[r], C.req_b[r]}] = (int)r;
   tan_off_ = C.req_tan_off; amb_off_ = C.req_amb_off;

@@ -7,31 +7,18 @@
 
 namespace sk {
 
-namespace {
-int tangent_of(const Problem& p, size_t b) {
-  const int pz = b < p.block_param.size() ? p.block_param[b] : -1;
-  return pz >= 0 ? p.params[pz].local_size : p.block_size[b];
-}
-}  // namespace
-
 std::string covariance_refusal(const Problem& p, bool schur) {
   char buf[320];
   for (size_t b = 0; b < p.rb_functor.size(); ++b)
     if (p.rb_functor[b] == SK_FUNCTOR_SYNTH_TANH_ROW)
       return "Covariance works on a block-sparse Jacobian: dense-row problems (sk_problem_add_dense_rows) are not supported";
+  const std::string too_large = block_size_refusal(p, "Covariance", kCovarianceMaxBlock, /*constants_too*/ true);
+  if (!too_large.empty()) return too_large;
   long long cols = 0;
   for (size_t b = 0; b < p.block_size.size(); ++b) {
+    if (b < p.block_constant.size() && p.block_constant[b]) continue;
     const int pz = b < p.block_param.size() ? p.block_param[b] : -1;
-    const int tangent = tangent_of(p, b);
-    if (pz >= 0 && p.block_size[b] > kCovarianceMaxBlock) {
-      snprintf(buf, sizeof(buf), "Covariance takes parameterized blocks of size up to %d (parameter block %d has %d: not supported)", kCovarianceMaxBlock, (int)b, p.block_size[b]);
-      return buf;
-    }
-    if (tangent > kCovarianceMaxBlock) {
-      snprintf(buf, sizeof(buf), "Covariance takes parameter blocks of tangent size up to %d (parameter block %d has %d: not supported)", kCovarianceMaxBlock, (int)b, tangent);
-      return buf;
-    }
-    if (!(b < p.block_constant.size() && p.block_constant[b])) cols += tangent;
+    cols += pz >= 0 ? p.params[pz].local_size : p.block_size[b];
   }
   if (!schur && cols > kCovarianceMaxColumns) {
     snprintf(buf, sizeof(buf),
@@ -44,27 +31,10 @@ std::string covariance_refusal(const Problem& p, bool schur) {
 }
 
 namespace {
-// the parts of term lists given by their [pairs + 1] ranges, exactly as the normal-matrix pairs are cut
-void cut_parts(const std::vector<int>& begin_of, std::vector<int>* part_pair, std::vector<int>* part_begin, std::vector<int>* part_end, std::vector<int>* part_out,
-               std::vector<int>* long_pair, std::vector<int>* long_begin, int* num_partials) {
-  const int npairs = (int)begin_of.size() - 1;
-  long_begin->push_back(0);
-  for (int q = 0; q < npairs; ++q) {
-    const int begin = begin_of[q], end = begin_of[q + 1];
-    const int nparts = std::max(1, (end - begin + kCgnrPartSlots - 1) / kCgnrPartSlots);
-    for (int k = 0; k < nparts; ++k) {
-      part_pair->push_back(q);
-      part_begin->push_back(begin + k * kCgnrPartSlots);
-      part_end->push_back(std::min(end, begin + (k + 1) * kCgnrPartSlots));
-      part_out->push_back(nparts == 1 ? -1 : (*num_partials)++);
-    }
-    if (nparts > 1) { long_pair->push_back(q); long_begin->push_back(*num_partials); }
-  }
-}
-
 // E, the routing of the pairs, F(e) and the Schur terms (covariance_plan.hpp); the columns, pairs, terms and parts of C are built
 int schur_plan_build(CovariancePlan& C, std::string* why) {
-  const int ncb = (int)C.cb_col.size(), npairs = (int)C.pair_i.size();
+  const TangentColumns& T = C.cols;
+  const int ncb = (int)T.cb_col.size(), npairs = (int)C.pair_i.size();
   C.schur = true;
   // neighbours: every off-diagonal pair names two
   std::vector<int> deg(ncb, 0), nb_begin(ncb + 1, 0);
@@ -85,7 +55,7 @@ int schur_plan_build(CovariancePlan& C, std::string* why) {
   long long red = 0;
   for (int c = 0; c < ncb; ++c) {
     if (C.cb_elim[c]) { C.cb_red[c] = (int)C.e_cb.size(); C.e_cb.push_back(c); }
-    else { C.cb_red[c] = (int)red; red += C.cb_size[c]; }
+    else { C.cb_red[c] = (int)red; red += T.cb_size[c]; }
   }
   C.num_elim = (int)C.e_cb.size();
   C.red_cols = (int)red;
@@ -125,7 +95,7 @@ int schur_plan_build(CovariancePlan& C, std::string* why) {
   char buf[320];
   if (C.red_cols > kCovarianceMaxColumns) {
     snprintf(buf, sizeof(buf), "Covariance with Schur elimination factors the dense reduced matrix and takes up to %d columns after the elimination (this problem keeps %d of %d: not supported)",
-             kCovarianceMaxColumns, C.red_cols, C.num_cols);
+             kCovarianceMaxColumns, C.red_cols, T.num_cols);
     if (why) *why = buf;
     return SK_ERR_UNSUPPORTED;
   }
@@ -140,7 +110,7 @@ int schur_plan_build(CovariancePlan& C, std::string* why) {
   for (int e = 0; e < C.num_elim; ++e)
     for (int k = C.ew_begin[e]; k < C.ew_begin[e + 1]; ++k)
       for (int l = C.ew_begin[e]; l <= k; ++l)
-        st.push_back(STerm{(long long)C.ew_g[k] * ncb + C.ew_g[l], C.ew_tile[k], C.ew_tile[l], C.cb_size[C.e_cb[e]]});
+        st.push_back(STerm{(long long)C.ew_g[k] * ncb + C.ew_g[l], C.ew_tile[k], C.ew_tile[l], T.cb_size[C.e_cb[e]]});
   std::stable_sort(st.begin(), st.end(), [](const STerm& a, const STerm& b) { return a.key < b.key; });
   C.st_a.reserve(st.size()); C.st_b.reserve(st.size()); C.st_ne.reserve(st.size());
   for (size_t t = 0; t < st.size(); ++t) {
@@ -148,7 +118,7 @@ int schur_plan_build(CovariancePlan& C, std::string* why) {
     C.st_a.push_back(st[t].a); C.st_b.push_back(st[t].b); C.st_ne.push_back(st[t].ne);
   }
   C.sp_begin.push_back((int)st.size());
-  cut_parts(C.sp_begin, &C.spart_pair, &C.spart_begin, &C.spart_end, &C.spart_out, &C.slong_pair, &C.slong_begin, &C.num_spartials);
+  cut_parts(C.sp_begin, &C.schur_parts);
   return SK_OK;
 }
 }  // namespace
@@ -163,27 +133,9 @@ int covariance_plan_build(const Problem& p, const std::vector<std::pair<int, int
   const EvaluatePlan& E = C.eval;
   const int num_pb = (int)p.block_ptr.size(), nb = (int)E.blocks.size();
 
-  // columns: the parameter blocks that move, as cgnr_plan_build takes them
-  C.block_off.assign(num_pb + 1, 0);
-  C.pb_type.resize(num_pb); C.pb_size.resize(num_pb); C.pb_local_size.resize(num_pb); C.pb_local_off.assign(num_pb, -1); C.pb_mask.resize(num_pb);
-  std::vector<int> cb_of(num_pb, -1);
-  int cols = 0;
-  for (int b = 0; b < num_pb; ++b) {
-    C.block_off[b + 1] = C.block_off[b] + p.block_size[b];
-    const int pz = b < (int)p.block_param.size() ? p.block_param[b] : -1;
-    const bool constant = b < (int)p.block_constant.size() && p.block_constant[b];
-    C.pb_type[b] = constant ? (int)kParamConstant : pz >= 0 ? p.params[pz].type : (int)kParamIdentity;
-    C.pb_mask[b] = pz >= 0 ? p.params[pz].constant_mask : 0u;
-    C.pb_size[b] = p.block_size[b];
-    C.pb_local_size[b] = E.col_size[b];
-    if (constant || E.col_size[b] == 0) continue;
-    C.pb_local_off[b] = cols;
-    cb_of[b] = (int)C.cb_col.size();
-    C.cb_col.push_back(cols); C.cb_size.push_back(E.col_size[b]); C.cb_block.push_back(b);
-    cols += E.col_size[b];
-  }
-  C.num_cols = cols;
-  const int ncb = (int)C.cb_col.size();
+  tangent_columns_build(p, E, ConstantTangent::kKeep, &C.cols);
+  const TangentColumns& T = C.cols;
+  const int ncb = (int)T.cb_col.size();
 
   // terms: per residual block every (slot of i, slot of j) with i >= j; a block that a residual block names twice has the two
   // cross terms of its diagonal pair in both orders (J_s^T J_t + J_t^T J_s)
@@ -195,7 +147,7 @@ int covariance_plan_build(const Problem& p, const std::vector<std::pair<int, int
     for (int s = E.slot_begin[i]; s < E.slot_begin[i + 1]; ++s) if (E.slot_pos[s] >= 0) stored.push_back(s);
     for (int s : stored)
       for (int t : stored) {
-        const int ci = cb_of[E.slot_block[s]], cj = cb_of[E.slot_block[t]];
+        const int ci = T.cb_of[E.slot_block[s]], cj = T.cb_of[E.slot_block[t]];
         if (ci < cj) continue;
         terms.push_back(Term{(long long)ci * ncb + cj, s, t});
       }
@@ -211,8 +163,7 @@ int covariance_plan_build(const Problem& p, const std::vector<std::pair<int, int
   }
   C.pair_begin.push_back((int)terms.size());
 
-  // parts: kCgnrPartSlots terms each, exactly as cgnr_plan_build cuts the slot lists
-  cut_parts(C.pair_begin, &C.part_pair, &C.part_begin, &C.part_end, &C.part_out, &C.long_pair, &C.long_begin, &C.num_partials);
+  cut_parts(C.pair_begin, &C.pair_parts);
   if (schur) {
     rc = schur_plan_build(C, why);
     if (rc != SK_OK) return rc;
@@ -223,18 +174,18 @@ int covariance_plan_build(const Problem& p, const std::vector<std::pair<int, int
   std::vector<int> sel_of(num_pb, -1);
   C.sel_off.push_back(0);
   auto select_cb = [&](int cb) {
-    const int b = C.cb_block[cb];
+    const int b = T.cb_block[cb];
     if (sel_of[b] >= 0) return;
     sel_of[b] = (int)C.sel_cb.size();
     C.sel_cb.push_back(cb);
-    for (int j = 0; j < C.cb_size[cb]; ++j) C.sel_col.push_back((schur ? C.cb_red[cb] : C.cb_col[cb]) + j);
+    for (int j = 0; j < T.cb_size[cb]; ++j) C.sel_col.push_back((schur ? C.cb_red[cb] : T.cb_col[cb]) + j);
     C.sel_off.push_back((int)C.sel_col.size());
   };
   auto select = [&](int b) {
-    if (cb_of[b] < 0) return;
-    if (!schur || !C.cb_elim[cb_of[b]]) { select_cb(cb_of[b]); return; }
-    const int e = C.cb_red[cb_of[b]];
-    for (int k = C.ew_begin[e]; k < C.ew_begin[e + 1]; ++k) { select_cb(C.ew_g[k]); C.ew_sel[k] = C.sel_off[sel_of[C.cb_block[C.ew_g[k]]]]; }
+    if (T.cb_of[b] < 0) return;
+    if (!schur || !C.cb_elim[T.cb_of[b]]) { select_cb(T.cb_of[b]); return; }
+    const int e = C.cb_red[T.cb_of[b]];
+    for (int k = C.ew_begin[e]; k < C.ew_begin[e + 1]; ++k) { select_cb(C.ew_g[k]); C.ew_sel[k] = C.sel_off[sel_of[T.cb_block[C.ew_g[k]]]]; }
   };
   std::map<std::pair<int, int>, int> seen;
   for (const auto& ab : pairs) {
@@ -250,13 +201,13 @@ int covariance_plan_build(const Problem& p, const std::vector<std::pair<int, int
   C.k = (int)C.sel_col.size();
   for (size_t r = 0; r < C.req_a.size(); ++r) {
     const int a = C.req_a[r], b = C.req_b[r];
-    const bool zero = cb_of[a] < 0 || cb_of[b] < 0;
-    const bool ea = schur && !zero && C.cb_elim[cb_of[a]], eb = schur && !zero && C.cb_elim[cb_of[b]];
+    const bool zero = T.cb_of[a] < 0 || T.cb_of[b] < 0;
+    const bool ea = schur && !zero && C.cb_elim[T.cb_of[a]], eb = schur && !zero && C.cb_elim[T.cb_of[b]];
     C.req_ra.push_back(zero ? -1 : ea ? 0 : C.sel_off[sel_of[a]]);
     C.req_rb.push_back(zero ? -1 : eb ? 0 : C.sel_off[sel_of[b]]);
-    if (schur) { C.req_ea.push_back(ea ? C.cb_red[cb_of[a]] : -1); C.req_eb.push_back(eb ? C.cb_red[cb_of[b]] : -1); }
-    C.req_tan_off.push_back(C.out_size); C.out_size += (long)C.pb_local_size[a] * C.pb_local_size[b];
-    C.req_amb_off.push_back(C.out_size); C.out_size += (long)C.pb_size[a] * C.pb_size[b];
+    if (schur) { C.req_ea.push_back(ea ? C.cb_red[T.cb_of[a]] : -1); C.req_eb.push_back(eb ? C.cb_red[T.cb_of[b]] : -1); }
+    C.req_tan_off.push_back(C.out_size); C.out_size += (long)T.pb_local_size[a] * T.pb_local_size[b];
+    C.req_amb_off.push_back(C.out_size); C.out_size += (long)T.pb_size[a] * T.pb_size[b];
   }
   return SK_OK;
 }

@@ -1,12 +1,12 @@
 // Host plan of sk_covariance_compute (covariance.hip): the block-sparse Jacobian's layout is Problem::Evaluate's (evaluate_plan.hpp)
-// over every residual block and every parameter block, the columns are CGNR's (cgnr_plan.hpp: the parameter blocks that move, in
-// problem order, each with its tangent size); this plan adds what the normal matrix H = J^T J and the selection of the requested
+// over every residual block and every parameter block, the columns are jacobian_plan.hpp's TangentColumns (the parameter blocks that
+// move, in problem order, each with its tangent size); this plan adds what the normal matrix H = J^T J and the selection of the requested
 // covariance blocks need — plain C++ over a Problem, compiled without the device headers like cgnr_plan.cpp.
 //
 // Normal-matrix pairs.  For every unordered pair of column blocks (i >= j by first column, i == j included) that share a
 // residual block, the TERMS of H_ij = sum J_i^T J_j: (slot of i, slot of j) of every residual block that stores both, in row order.
-// A term list is cut into PARTS of cgnr::kPartSlots (64) terms, the last one shorter; a pair of more than one part (a LONG pair: a
-// camera's diagonal, a hub of a chain) leaves one partial tile per part, which a second launch adds in part order.  Pairs, terms
+// A term list is cut into PARTS of cgnr::kPartSlots (64) terms (jacobian_plan.hpp: cut_parts); a pair of more than one part (a LONG pair:
+// a camera's diagonal, a hub of a chain) leaves one partial tile per part, which a second launch adds in part order.  Pairs, terms
 // and parts are fixed here: the sum of a tile depends on the problem alone, and no launch uses a floating-point atomic.
 //
 // Selection.  The distinct moving column blocks named by the requested pairs, in order of first appearance; their k columns are
@@ -42,20 +42,12 @@ constexpr int kCovarianceTile = 256;                // entries of a partial tile
 
 struct CovariancePlan {
   EvaluatePlan eval;  // staging sized for residuals + Jacobian planes
-  int num_cols = 0;   // N: the tangent size of the problem
-  std::vector<int> block_off;                                       // [parameter blocks + 1] in x
-  std::vector<int> pb_type, pb_size, pb_local_size, pb_local_off;   // per parameter block: ParameterizationType (kParamConstant for constant blocks), size, tangent
-                                                                    // size (Problem::Evaluate's, kept for a constant block) and first column (-1: constant, or tangent size 0)
-  std::vector<unsigned> pb_mask;
-  std::vector<int> cb_col, cb_size, cb_block;  // column blocks (the parameter blocks that move): first column, tangent size, parameter block
+  TangentColumns cols;  // num_cols is N; a constant block keeps Problem::Evaluate's tangent size (its covariance block is zero, of that shape)
   // the normal matrix
   std::vector<int> pair_i, pair_j;      // column blocks, first column of i >= first column of j
   std::vector<int> pair_begin;          // [pairs + 1] into term_si / term_sj
   std::vector<int> term_si, term_sj;    // slots of eval, both of one residual block
-  std::vector<int> part_pair, part_begin, part_end;  // the pair; the part's range of terms
-  std::vector<int> part_out;                         // -1: the pair's only part; else the index of its partial tile
-  std::vector<int> long_pair, long_begin;            // long pairs; [long pairs + 1] their ranges of partial tiles
-  int num_partials = 0;
+  PartList pair_parts;                  // of the term lists, in pair order; a partial sum is a tile
   // the selection
   std::vector<int> sel_cb;   // selected column blocks, in order of first appearance
   std::vector<int> sel_off;  // [selected + 1] first of the block's columns among the k selected ones
@@ -78,8 +70,7 @@ struct CovariancePlan {
   std::vector<int> ew_tile, ew_g, ew_sel;     // the (g, e) tile, the F column block g, g's first row among the k selected ones (-1: e was not requested)
   std::vector<int> sp_i, sp_j, sp_begin;      // pairs of F blocks with Schur terms; [pairs + 1] into st_*
   std::vector<int> st_a, st_b, st_ne;         // tile of (g, e), tile of (g', e), tangent size of e
-  std::vector<int> spart_pair, spart_begin, spart_end, spart_out, slong_pair, slong_begin;  // as part_* / long_* above
-  int num_spartials = 0;
+  PartList schur_parts;                       // of the Schur terms, in sp_* order
   std::vector<int> req_ea, req_eb;            // per requested pair: the e-block index of a / b (-1: in F, req_ra / req_rb hold its rows)
 };
 

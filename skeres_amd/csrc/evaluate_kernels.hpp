@@ -69,11 +69,10 @@ void launch_evaluate_cost(const double* cterm, int n, double* partials, double* 
 
 // sk_problem_evaluate (evaluate.hip).  Every output may be null.  launch_seconds (may be null): device seconds of the call's
 // phases from HIP events on its stream — 0 uploads, 1 evaluation launches (with the host callbacks), 2 finish, 3 gradient, 4 cost,
-// 5 downloads.  keep_values (may be null): takes over the device copy of the values array, which is then computed whether or not
-// `values` is given (sk_covariance_compute reads it where it lies).
+// 5 downloads.
 struct EvaluateOptions;
 constexpr int kEvaluatePhases = 6;
 int problem_evaluate(const Problem& p, const EvaluateOptions* options, double* cost, double* residuals, double* gradient, double* values,
-                     double* launch_seconds, DevBuf<double>* keep_values = nullptr);
+                     double* launch_seconds);
 
 }  // namespace sk

@@ -17,6 +17,20 @@ int fail(std::string* why, int status, const char* fmt, long long a = 0, long lo
 }
 }  // namespace
 
+size_t evaluate_plan_staging(const EvaluatePlan& plan, bool jacobian, std::vector<size_t>* group_stage, std::vector<size_t>* blk_stage, std::vector<int>* blk_stride) {
+  size_t stage = 0;
+  group_stage->clear();
+  blk_stage->resize(plan.blocks.size());
+  if (blk_stride) blk_stride->resize(plan.blocks.size());
+  for (const EvaluateGroup& G : plan.groups) {
+    group_stage->push_back(stage);
+    const size_t count = G.members.size();
+    for (size_t l = 0; l < count; ++l) { (*blk_stage)[G.members[l]] = stage + l; if (blk_stride) (*blk_stride)[G.members[l]] = (int)count; }
+    stage += count * (size_t)G.num_residuals * (size_t)(jacobian ? 1 + G.dim : 1);
+  }
+  return stage;
+}
+
 int evaluate_plan_build(const Problem& p, const EvaluateOptions* options, bool structure, bool gradient, bool jacobian, EvaluatePlan* plan,
                         std::string* why) {
   static const EvaluateOptions kDefaults;
@@ -72,7 +86,6 @@ int evaluate_plan_build(const Problem& p, const EvaluateOptions* options, bool s
   }
   const int nb = (int)P.blocks.size();
   P.row_off.resize(nb + 1); P.val_off.resize(nb + 1); P.slot_begin.resize(nb + 1);
-  P.blk_stage.resize(nb); P.blk_stride.resize(nb);
   long long rows = 0, nnz = 0;
   std::map<int, int> group_of;       // functor -> group
   std::vector<int> callback_blocks;  // listed positions
@@ -119,17 +132,15 @@ int evaluate_plan_build(const Problem& p, const EvaluateOptions* options, bool s
     EvaluateGroup& G = P.groups.back();
     G.functor = SK_FUNCTOR_HOST_CALLBACK; G.num_residuals = p.rb_num_residuals[P.blocks[i]]; G.dim = dim_of(i); G.members.push_back(i);
   }
-  size_t stage = 0;
+  std::vector<size_t> group_stage;
+  P.stage_size = evaluate_plan_staging(P, jacobian, &group_stage, &P.blk_stage, &P.blk_stride);
   bool in_callbacks = false;
-  for (EvaluateGroup& G : P.groups) {
-    if (G.functor == SK_FUNCTOR_HOST_CALLBACK && !in_callbacks) { in_callbacks = true; P.callback_stage_begin = stage; }
-    G.stage_off = stage;
-    const size_t count = G.members.size();
-    for (size_t l = 0; l < count; ++l) { P.blk_stage[G.members[l]] = stage + l; P.blk_stride[G.members[l]] = (int)count; }
-    stage += count * (size_t)G.num_residuals * (size_t)(jacobian ? 1 + G.dim : 1);
+  for (size_t g = 0; g < P.groups.size(); ++g) {
+    EvaluateGroup& G = P.groups[g];
+    G.stage_off = group_stage[g];
+    if (G.functor == SK_FUNCTOR_HOST_CALLBACK && !in_callbacks) { in_callbacks = true; P.callback_stage_begin = G.stage_off; }
   }
-  if (!in_callbacks) P.callback_stage_begin = stage;
-  P.stage_size = stage;
+  if (!in_callbacks) P.callback_stage_begin = P.stage_size;
 
   if (gradient) {
     std::vector<int> cb_of(num_pb, -1);

@@ -62,5 +62,10 @@ struct EvaluatePlan {
 // staging holds the Jacobian planes too (else the num_residuals residual planes of every group alone).
 int evaluate_plan_build(const Problem& p, const EvaluateOptions* options, bool structure, bool gradient, bool jacobian, EvaluatePlan* plan,
                         std::string* why);
+// The staging of the plan's groups, as evaluate_plan_build lays it out for `jacobian`: per group its stage_off, per listed block
+// its blk_stage (and its blk_stride, where asked for); returns the stage_size.  With jacobian == false on a plan built with the
+// Jacobian planes: where a residual-only evaluation of the same groups puts its results (blk_stride is the same).
+size_t evaluate_plan_staging(const EvaluatePlan& plan, bool jacobian, std::vector<size_t>* group_stage, std::vector<size_t>* blk_stage,
+                             std::vector<int>* blk_stride = nullptr);
 
 }  // namespace sk

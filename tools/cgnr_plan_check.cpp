@@ -4,7 +4,8 @@
 // Meant to be compiled with the host compiler under -fsanitize=address,undefined (no device code, no HIP):
 //
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include \
-//       tools/cgnr_plan_check.cpp skeres_amd/csrc/cgnr_plan.cpp skeres_amd/csrc/evaluate_plan.cpp -o cgnr_plan_check && ./cgnr_plan_check
+//       tools/cgnr_plan_check.cpp skeres_amd/csrc/cgnr_plan.cpp skeres_amd/csrc/jacobian_plan.cpp skeres_amd/csrc/evaluate_plan.cpp -o cgnr_plan_check && ./cgnr_plan_check
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -44,17 +45,17 @@ int main() {
   std::string why;
   REQUIRE(cgnr_plan_build(p, &C, &why) == SK_OK);
   const EvaluatePlan& E = C.eval;
-  const int ncb = (int)C.cb_col.size(), ns = (int)E.slot_block.size(), nparts = (int)C.part_cb.size();
-  REQUIRE(C.num_ambient == 2 * nblocks && C.num_cols == 2 * (nblocks - 2) && ncb == nblocks - 2);
+  const int ncb = (int)C.cols.cb_col.size(), ns = (int)E.slot_block.size(), nparts = (int)C.parts.owner.size();
+  REQUIRE(C.cols.num_ambient == 2 * nblocks && C.cols.num_cols == 2 * (nblocks - 2) && ncb == nblocks - 2);
   REQUIRE(E.num_rows == 3 * (nblocks - 1 + hub_blocks) && (int)C.row_block.size() == E.num_rows);
   // every stored slot once in exactly one column block's list, in ascending order; the values stay inside the array
   std::vector<int> seen(ns, 0);
   long long stored = 0;
   for (int c = 0; c < ncb; ++c) {
-    REQUIRE(C.cb_size[c] == 2 && C.cb_col[c] == 2 * c && C.cb_moff[c + 1] - C.cb_moff[c] == 4);
+    REQUIRE(C.cols.cb_size[c] == 2 && C.cols.cb_col[c] == 2 * c && C.cb_moff[c + 1] - C.cb_moff[c] == 4);
     for (int k = C.cb_begin[c]; k < C.cb_begin[c + 1]; ++k) {
       const int s = C.cb_slots[k];
-      REQUIRE(s >= 0 && s < ns && !seen[s]++ && C.slot_col[s] == C.cb_col[c] && C.slot_size[s] == C.cb_size[c]);
+      REQUIRE(s >= 0 && s < ns && !seen[s]++ && C.slot_col[s] == C.cols.cb_col[c] && C.slot_size[s] == C.cols.cb_size[c]);
       REQUIRE(k == C.cb_begin[c] || C.cb_slots[k - 1] < s);
       const int i = E.slot_owner[s], nres = E.row_off[i + 1] - E.row_off[i], width = (E.val_off[i + 1] - E.val_off[i]) / nres;
       REQUIRE(E.slot_pos[s] >= 0 && E.slot_pos[s] + C.slot_size[s] <= width && E.val_off[i + 1] <= E.num_nonzeros);
@@ -69,18 +70,46 @@ int main() {
     const int begin = C.cb_begin[c], end = C.cb_begin[c + 1], first = part;
     int at = begin;
     do {
-      REQUIRE(part < nparts && C.part_cb[part] == c && C.part_begin[part] == at);
-      REQUIRE(C.part_end[part] == (at + kCgnrPartSlots < end ? at + kCgnrPartSlots : end));
-      at = C.part_end[part++];
+      REQUIRE(part < nparts && C.parts.owner[part] == c && C.parts.begin[part] == at);
+      REQUIRE(C.parts.end[part] == (at + kCgnrPartSlots < end ? at + kCgnrPartSlots : end));
+      at = C.parts.end[part++];
     } while (at < end);
-    if (part - first == 1) { REQUIRE(C.part_out[first] == -1); continue; }
-    REQUIRE(C.long_cb[nlong] == c && C.long_begin[nlong] == partial);
-    for (int k = first; k < part; ++k) REQUIRE(C.part_out[k] == partial++);
-    REQUIRE(C.long_begin[++nlong] == partial);
+    if (part - first == 1) { REQUIRE(C.parts.out[first] == -1); continue; }
+    REQUIRE(C.parts.long_owner[nlong] == c && C.parts.long_begin[nlong] == partial);
+    for (int k = first; k < part; ++k) REQUIRE(C.parts.out[k] == partial++);
+    REQUIRE(C.parts.long_begin[++nlong] == partial);
   }
-  REQUIRE(part == nparts && partial == C.num_partials && nlong == (int)C.long_cb.size());
-  REQUIRE(nlong == 1 && C.num_partials == (hub_blocks + 2 + kCgnrPartSlots - 1) / kCgnrPartSlots);   // the hub: 320 + its two neighbours
+  REQUIRE(part == nparts && partial == C.parts.num_partials && nlong == (int)C.parts.long_owner.size());
+  REQUIRE(nlong == 1 && C.parts.num_partials == (hub_blocks + 2 + kCgnrPartSlots - 1) / kCgnrPartSlots);   // the hub: 320 + its two neighbours
   REQUIRE(C.blk_stage_cost.size() == E.blk_stage.size() && C.group_stage_cost.size() == E.groups.size());
   printf("cgnr_plan_check ok: %d column blocks, %d parts, %d long, %lld stored entries\n", ncb, nparts, nlong, E.num_nonzeros);
+
+  // cut_parts by itself: owners with lists of 0, 1, 64, 65 and 129 entries in one call
+  const int lengths[5] = {0, 1, 64, 65, 129}, want_parts[5] = {1, 1, 1, 2, 3};
+  std::vector<int> begin_of(1, 0);
+  for (int len : lengths) begin_of.push_back(begin_of.back() + len);
+  PartList L;
+  cut_parts(begin_of, &L);
+  const size_t total = 1 + 1 + 1 + 2 + 3;
+  REQUIRE(L.owner.size() == total && L.begin.size() == total && L.end.size() == total && L.out.size() == total);
+  int k = 0, partials = 0, longs = 0;
+  REQUIRE(L.long_begin.size() >= 1 && L.long_begin[0] == 0);
+  for (int q = 0; q < 5; ++q) {
+    int at = begin_of[q];
+    for (int j = 0; j < want_parts[q]; ++j, ++k) {
+      REQUIRE(L.owner[k] == q && L.begin[k] == at && L.end[k] == std::min(at + kCgnrPartSlots, begin_of[q + 1]) && L.end[k] >= L.begin[k]);
+      REQUIRE(L.out[k] == (want_parts[q] == 1 ? -1 : partials));   // -1 exactly for the owners of one part
+      if (want_parts[q] > 1) ++partials;
+      at = L.end[k];
+    }
+    REQUIRE(at == begin_of[q + 1]);
+    if (want_parts[q] == 1) continue;
+    REQUIRE(longs < (int)L.long_owner.size() && L.long_owner[longs] == q);
+    REQUIRE(L.long_begin[longs] < L.long_begin[longs + 1] && L.long_begin[longs + 1] == partials);   // monotone
+    ++longs;
+  }
+  REQUIRE(L.begin[0] == 0 && L.end[0] == 0);   // the empty owner: one empty part
+  REQUIRE(longs == 2 && (int)L.long_owner.size() == longs && (int)L.long_begin.size() == longs + 1 && L.long_begin.back() == L.num_partials && L.num_partials == 5);
+  printf("cgnr_plan_check cut_parts ok: %zu parts, %d long, %d partial sums\n", total, longs, L.num_partials);
   return 0;
 }

@@ -7,7 +7,7 @@
 // Meant to be compiled with the host compiler under -fsanitize=address,undefined (no device code, no HIP):
 //
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include tools/covariance_plan_check.cpp \
-//       skeres_amd/csrc/covariance_plan.cpp skeres_amd/csrc/evaluate_plan.cpp -o covariance_plan_check && ./covariance_plan_check
+//       skeres_amd/csrc/covariance_plan.cpp skeres_amd/csrc/jacobian_plan.cpp skeres_amd/csrc/evaluate_plan.cpp -o covariance_plan_check && ./covariance_plan_check
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -46,18 +46,18 @@ struct Builder {
 // the plan against a brute-force enumeration of the problem's structure
 int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, const CovariancePlan& C) {
   const EvaluatePlan& E = C.eval;
-  const int num_pb = (int)p.block_ptr.size(), ncb = (int)C.cb_col.size(), nb = (int)E.blocks.size(), npairs = (int)C.pair_i.size();
+  const int num_pb = (int)p.block_ptr.size(), ncb = (int)C.cols.cb_col.size(), nb = (int)E.blocks.size(), npairs = (int)C.pair_i.size();
   // columns
   int cols = 0;
   std::vector<int> cb_of(num_pb, -1);
   for (int c = 0; c < ncb; ++c) {
-    const int b = C.cb_block[c];
-    REQUIRE(b >= 0 && b < num_pb && !p.block_constant[b] && C.cb_col[c] == cols && C.cb_size[c] == E.col_size[b] && C.cb_size[c] > 0 && C.cb_size[c] <= kCovarianceMaxBlock);
-    REQUIRE(C.pb_local_off[b] == cols && (c == 0 || C.cb_block[c - 1] < b));
-    cb_of[b] = c; cols += C.cb_size[c];
+    const int b = C.cols.cb_block[c];
+    REQUIRE(b >= 0 && b < num_pb && !p.block_constant[b] && C.cols.cb_col[c] == cols && C.cols.cb_size[c] == E.col_size[b] && C.cols.cb_size[c] > 0 && C.cols.cb_size[c] <= kCovarianceMaxBlock);
+    REQUIRE(C.cols.pb_local_off[b] == cols && (c == 0 || C.cols.cb_block[c - 1] < b));
+    cb_of[b] = c; cols += C.cols.cb_size[c];
   }
-  REQUIRE(cols == C.num_cols);
-  for (int b = 0; b < num_pb; ++b) REQUIRE((cb_of[b] >= 0) == (C.pb_local_off[b] >= 0) && (cb_of[b] >= 0 || p.block_constant[b] || E.col_size[b] == 0));
+  REQUIRE(cols == C.cols.num_cols);
+  for (int b = 0; b < num_pb; ++b) REQUIRE((cb_of[b] >= 0) == (C.cols.pb_local_off[b] >= 0) && (cb_of[b] >= 0 || p.block_constant[b] || E.col_size[b] == 0));
   // terms: the brute-force lists per (i, j), in row order
   std::map<std::pair<int, int>, std::vector<std::pair<int, int>>> want;
   for (int i = 0; i < nb; ++i)
@@ -71,34 +71,34 @@ int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, cons
   REQUIRE((int)want.size() == npairs && (int)C.pair_begin.size() == npairs + 1 && C.pair_begin[npairs] == (int)C.term_si.size());
   int q = 0;
   for (const auto& kv : want) {   // (the map's order is the plan's: by i, then j)
-    REQUIRE(C.pair_i[q] == kv.first.first && C.pair_j[q] == kv.first.second && C.cb_col[C.pair_i[q]] >= C.cb_col[C.pair_j[q]]);
+    REQUIRE(C.pair_i[q] == kv.first.first && C.pair_j[q] == kv.first.second && C.cols.cb_col[C.pair_i[q]] >= C.cols.cb_col[C.pair_j[q]]);
     REQUIRE(C.pair_begin[q + 1] - C.pair_begin[q] == (int)kv.second.size());
     for (size_t k = 0; k < kv.second.size(); ++k) {
       const int si = C.term_si[C.pair_begin[q] + k], sj = C.term_sj[C.pair_begin[q] + k];
       REQUIRE(si == kv.second[k].first && sj == kv.second[k].second && E.slot_owner[si] == E.slot_owner[sj]);
       const int i = E.slot_owner[si], nres = E.row_off[i + 1] - E.row_off[i], width = (E.val_off[i + 1] - E.val_off[i]) / nres;
-      REQUIRE(E.slot_pos[si] + C.cb_size[C.pair_i[q]] <= width && E.slot_pos[sj] + C.cb_size[C.pair_j[q]] <= width && E.val_off[i + 1] <= E.num_nonzeros);
+      REQUIRE(E.slot_pos[si] + C.cols.cb_size[C.pair_i[q]] <= width && E.slot_pos[sj] + C.cols.cb_size[C.pair_j[q]] <= width && E.val_off[i + 1] <= E.num_nonzeros);
     }
     ++q;
   }
   // parts
-  const int nparts = (int)C.part_pair.size();
+  const int nparts = (int)C.pair_parts.owner.size();
   int part = 0, partial = 0, nlong = 0;
   for (q = 0; q < npairs; ++q) {
     const int begin = C.pair_begin[q], end = C.pair_begin[q + 1], first = part;
     REQUIRE(end > begin);
     int at = begin;
     do {
-      REQUIRE(part < nparts && C.part_pair[part] == q && C.part_begin[part] == at);
-      REQUIRE(C.part_end[part] == (at + kCgnrPartSlots < end ? at + kCgnrPartSlots : end));
-      at = C.part_end[part++];
+      REQUIRE(part < nparts && C.pair_parts.owner[part] == q && C.pair_parts.begin[part] == at);
+      REQUIRE(C.pair_parts.end[part] == (at + kCgnrPartSlots < end ? at + kCgnrPartSlots : end));
+      at = C.pair_parts.end[part++];
     } while (at < end);
-    if (part - first == 1) { REQUIRE(C.part_out[first] == -1); continue; }
-    REQUIRE(C.long_pair[nlong] == q && C.long_begin[nlong] == partial);
-    for (int k = first; k < part; ++k) REQUIRE(C.part_out[k] == partial++);
-    REQUIRE(C.long_begin[++nlong] == partial);
+    if (part - first == 1) { REQUIRE(C.pair_parts.out[first] == -1); continue; }
+    REQUIRE(C.pair_parts.long_owner[nlong] == q && C.pair_parts.long_begin[nlong] == partial);
+    for (int k = first; k < part; ++k) REQUIRE(C.pair_parts.out[k] == partial++);
+    REQUIRE(C.pair_parts.long_begin[++nlong] == partial);
   }
-  REQUIRE(part == nparts && partial == C.num_partials && nlong == (int)C.long_pair.size() && (int)C.long_begin.size() == nlong + 1);
+  REQUIRE(part == nparts && partial == C.pair_parts.num_partials && nlong == (int)C.pair_parts.long_owner.size() && (int)C.pair_parts.long_begin.size() == nlong + 1);
   // the selection: moving blocks named by the pairs, in order of first appearance; columns inside H
   std::vector<int> order;
   for (const auto& ab : pairs)
@@ -109,8 +109,8 @@ int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, cons
     }
   REQUIRE(order.size() == C.sel_cb.size() && C.sel_off.size() == order.size() + 1 && C.k == (int)C.sel_col.size() && C.sel_off.back() == C.k);
   for (size_t i = 0; i < order.size(); ++i) {
-    REQUIRE(C.sel_cb[i] == cb_of[order[i]] && C.sel_off[i + 1] - C.sel_off[i] == C.cb_size[C.sel_cb[i]]);
-    for (int j = 0; j < C.cb_size[C.sel_cb[i]]; ++j) REQUIRE(C.sel_col[C.sel_off[i] + j] == C.cb_col[C.sel_cb[i]] + j && C.sel_col[C.sel_off[i] + j] < C.num_cols);
+    REQUIRE(C.sel_cb[i] == cb_of[order[i]] && C.sel_off[i + 1] - C.sel_off[i] == C.cols.cb_size[C.sel_cb[i]]);
+    for (int j = 0; j < C.cols.cb_size[C.sel_cb[i]]; ++j) REQUIRE(C.sel_col[C.sel_off[i] + j] == C.cols.cb_col[C.sel_cb[i]] + j && C.sel_col[C.sel_off[i] + j] < C.cols.num_cols);
   }
   // the requested pairs: each unordered pair once; blocks of the packed output do not overlap and fill it
   std::map<std::pair<int, int>, int> once;
@@ -122,7 +122,7 @@ int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, cons
     REQUIRE((C.req_ra[r] < 0) == zero && (C.req_rb[r] < 0) == zero);
     if (!zero) {
       REQUIRE(C.req_ra[r] + E.col_size[a] <= C.k && C.req_rb[r] + E.col_size[b] <= C.k);
-      REQUIRE(C.sel_col[C.req_ra[r]] == C.pb_local_off[a] && C.sel_col[C.req_rb[r]] == C.pb_local_off[b]);
+      REQUIRE(C.sel_col[C.req_ra[r]] == C.cols.pb_local_off[a] && C.sel_col[C.req_rb[r]] == C.cols.pb_local_off[b]);
     }
     REQUIRE(C.req_tan_off[r] == at); at += (long)E.col_size[a] * E.col_size[b];
     REQUIRE(C.req_amb_off[r] == at); at += (long)p.block_size[a] * p.block_size[b];
@@ -148,10 +148,10 @@ int main() {
     CovariancePlan C;
     REQUIRE(covariance_plan_build(B.p, pairs, &C, &why) == SK_OK);
     REQUIRE(verify(B.p, pairs, C) == 0);
-    REQUIRE(C.num_cols == 2 * (nblocks - 2) && C.k == 10 && C.req_a.size() == 5);          // hub, 0, last, 6, 5; the duplicates and the swap collapse
-    REQUIRE(C.long_pair.size() == 1 && C.num_partials == (hub_blocks + 2 + kCgnrPartSlots - 1) / kCgnrPartSlots);   // the hub's diagonal: 320 + its two neighbours
-    printf("covariance_plan_check chain ok: %d columns, %zu pairs, %zu terms, %zu parts, %d partial tiles, k = %d\n", C.num_cols, C.pair_i.size(), C.term_si.size(),
-           C.part_pair.size(), C.num_partials, C.k);
+    REQUIRE(C.cols.num_cols == 2 * (nblocks - 2) && C.k == 10 && C.req_a.size() == 5);          // hub, 0, last, 6, 5; the duplicates and the swap collapse
+    REQUIRE(C.pair_parts.long_owner.size() == 1 && C.pair_parts.num_partials == (hub_blocks + 2 + kCgnrPartSlots - 1) / kCgnrPartSlots);   // the hub's diagonal: 320 + its two neighbours
+    printf("covariance_plan_check chain ok: %d columns, %zu pairs, %zu terms, %zu parts, %d partial tiles, k = %d\n", C.cols.num_cols, C.pair_i.size(), C.term_si.size(),
+           C.pair_parts.owner.size(), C.pair_parts.num_partials, C.k);
   }
   {  // a bundle-adjustment shape: 5 cameras of 9, 40 points of 3, three observations per point, one pair observed twice
     const int ncam = 5, npt = 40;
@@ -170,13 +170,13 @@ int main() {
     CovariancePlan C;
     REQUIRE(covariance_plan_build(B.p, pairs, &C, &why) == SK_OK);
     REQUIRE(verify(B.p, pairs, C) == 0);
-    REQUIRE(C.num_cols == 9 * 3 + 6 + 3 * npt + 4 && C.k == 3 + 9 + 6 + 9 + 4 + 3);
+    REQUIRE(C.cols.num_cols == 9 * 3 + 6 + 3 * npt + 4 && C.k == 3 + 9 + 6 + 9 + 4 + 3);
     bool two_terms = false;
     for (size_t q = 0; q < C.pair_i.size(); ++q)
-      two_terms = two_terms || (C.cb_block[C.pair_i[q]] == cam(1) && C.cb_block[C.pair_j[q]] == pt(0) && C.pair_begin[q + 1] - C.pair_begin[q] == 2);   // (point 0 was named first: the lower column)
+      two_terms = two_terms || (C.cols.cb_block[C.pair_i[q]] == cam(1) && C.cols.cb_block[C.pair_j[q]] == pt(0) && C.pair_begin[q + 1] - C.pair_begin[q] == 2);   // (point 0 was named first: the lower column)
     REQUIRE(two_terms);
-    for (size_t q = 0; q < C.pair_i.size(); ++q) REQUIRE(C.cb_block[C.pair_i[q]] != lone);   // no pair: its diagonal stays zero, and the device flags it
-    printf("covariance_plan_check bundle-adjustment shape ok: %d columns, %zu pairs, %zu terms, k = %d\n", C.num_cols, C.pair_i.size(), C.term_si.size(), C.k);
+    for (size_t q = 0; q < C.pair_i.size(); ++q) REQUIRE(C.cols.cb_block[C.pair_i[q]] != lone);   // no pair: its diagonal stays zero, and the device flags it
+    printf("covariance_plan_check bundle-adjustment shape ok: %d columns, %zu pairs, %zu terms, k = %d\n", C.cols.num_cols, C.pair_i.size(), C.term_si.size(), C.k);
     const std::vector<std::pair<int, int>> bad = {{0, (int)B.p.block_ptr.size()}};
     REQUIRE(covariance_plan_build(B.p, bad, &C, &why) == SK_ERR_INVALID_ARGUMENT);
   }

@@ -9,7 +9,7 @@
 // Meant to be compiled with the host compiler under -fsanitize=address,undefined (no device code, no HIP):
 //
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include tools/covariance_schur_plan_check.cpp \
-//       skeres_amd/csrc/covariance_plan.cpp skeres_amd/csrc/evaluate_plan.cpp -o covariance_schur_plan_check && ./covariance_schur_plan_check
+//       skeres_amd/csrc/covariance_plan.cpp skeres_amd/csrc/jacobian_plan.cpp skeres_amd/csrc/evaluate_plan.cpp -o covariance_schur_plan_check && ./covariance_schur_plan_check
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -48,7 +48,7 @@ struct Builder {
 };
 
 int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, const CovariancePlan& C) {
-  const int ncb = (int)C.cb_col.size(), npairs = (int)C.pair_i.size(), nE = C.num_elim;
+  const int ncb = (int)C.cols.cb_col.size(), npairs = (int)C.pair_i.size(), nE = C.num_elim;
   REQUIRE(C.schur && (int)C.cb_elim.size() == ncb && (int)C.cb_red.size() == ncb && (int)C.e_cb.size() == nE);
   // E is independent; the greedy rule restated: ascending (distinct neighbours, parameter block), join when no neighbour has joined
   std::vector<std::set<int>> nb(ncb);
@@ -64,7 +64,7 @@ int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, cons
   int red = 0, e = 0;
   for (int c = 0; c < ncb; ++c) {
     if (C.cb_elim[c]) { REQUIRE(C.cb_red[c] == e && C.e_cb[e] == c); ++e; }
-    else { REQUIRE(C.cb_red[c] == red); red += C.cb_size[c]; }
+    else { REQUIRE(C.cb_red[c] == red); red += C.cols.cb_size[c]; }
   }
   REQUIRE(e == nE && red == C.red_cols && red <= kCovarianceMaxColumns);
   // the routing: every pair to the dense matrix or to one tile; tiles are distinct and inside the buffer
@@ -73,7 +73,7 @@ int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, cons
   std::map<std::pair<int, int>, int> tile_of;  // (g, e as column blocks) -> tile
   for (int q = 0; q < npairs; ++q) {
     const int i = C.pair_i[q], j = C.pair_j[q], t = C.pair_tile[q];
-    if (!C.cb_elim[i] && !C.cb_elim[j]) { REQUIRE(t == -1); REQUIRE(C.cb_red[i] + C.cb_size[i] <= C.red_cols && C.cb_red[j] + C.cb_size[j] <= C.red_cols); continue; }
+    if (!C.cb_elim[i] && !C.cb_elim[j]) { REQUIRE(t == -1); REQUIRE(C.cb_red[i] + C.cols.cb_size[i] <= C.red_cols && C.cb_red[j] + C.cols.cb_size[j] <= C.red_cols); continue; }
     REQUIRE(t >= 0 && t < C.num_tiles && tiles.insert(t).second);
     if (i == j) { REQUIRE(t == C.cb_red[i] && !C.pair_flip[q]); continue; }
     REQUIRE(t >= 2 * nE && C.pair_flip[q] == C.cb_elim[i]);
@@ -110,36 +110,36 @@ int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, cons
     for (int k = C.sp_begin[q]; k < C.sp_begin[q + 1]; ++k) {
       const int a = C.st_a[k], b = C.st_b[k];
       REQUIRE(a >= 2 * nE && a < C.num_tiles && b >= 2 * nE && b < C.num_tiles && g_of_tile[a] == g && g_of_tile[b] == h);
-      REQUIRE(e_of_tile[a] >= 0 && e_of_tile[a] == e_of_tile[b] && C.st_ne[k] == C.cb_size[C.e_cb[e_of_tile[a]]]);
+      REQUIRE(e_of_tile[a] >= 0 && e_of_tile[a] == e_of_tile[b] && C.st_ne[k] == C.cols.cb_size[C.e_cb[e_of_tile[a]]]);
       REQUIRE(k == C.sp_begin[q] || e_of_tile[C.st_a[k - 1]] < e_of_tile[a]);
     }
   }
   // the parts tile the term lists
-  const int nparts = (int)C.spart_pair.size();
+  const int nparts = (int)C.schur_parts.owner.size();
   int part = 0, partial = 0, nlong = 0;
   for (int q = 0; q < nsp; ++q) {
     const int begin = C.sp_begin[q], end = C.sp_begin[q + 1], first = part;
     int at = begin;
     do {
-      REQUIRE(part < nparts && C.spart_pair[part] == q && C.spart_begin[part] == at);
-      REQUIRE(C.spart_end[part] == (at + kCgnrPartSlots < end ? at + kCgnrPartSlots : end));
-      at = C.spart_end[part++];
+      REQUIRE(part < nparts && C.schur_parts.owner[part] == q && C.schur_parts.begin[part] == at);
+      REQUIRE(C.schur_parts.end[part] == (at + kCgnrPartSlots < end ? at + kCgnrPartSlots : end));
+      at = C.schur_parts.end[part++];
     } while (at < end);
-    if (part - first == 1) { REQUIRE(C.spart_out[first] == -1); continue; }
-    REQUIRE(C.slong_pair[nlong] == q && C.slong_begin[nlong] == partial);
-    for (int k = first; k < part; ++k) REQUIRE(C.spart_out[k] == partial++);
-    REQUIRE(C.slong_begin[++nlong] == partial);
+    if (part - first == 1) { REQUIRE(C.schur_parts.out[first] == -1); continue; }
+    REQUIRE(C.schur_parts.long_owner[nlong] == q && C.schur_parts.long_begin[nlong] == partial);
+    for (int k = first; k < part; ++k) REQUIRE(C.schur_parts.out[k] == partial++);
+    REQUIRE(C.schur_parts.long_begin[++nlong] == partial);
   }
-  REQUIRE(part == nparts && partial == C.num_spartials && nlong == (int)C.slong_pair.size() && (int)C.slong_begin.size() == nlong + 1);
+  REQUIRE(part == nparts && partial == C.schur_parts.num_partials && nlong == (int)C.schur_parts.long_owner.size() && (int)C.schur_parts.long_begin.size() == nlong + 1);
   // the selection: F blocks only, columns of the reduced matrix; a requested e-block has all of F(e) selected
   std::vector<int> cb_of(p.block_ptr.size(), -1), sel_row(ncb, -1);
-  for (int c = 0; c < ncb; ++c) cb_of[C.cb_block[c]] = c;
+  for (int c = 0; c < ncb; ++c) cb_of[C.cols.cb_block[c]] = c;
   REQUIRE(C.sel_off.size() == C.sel_cb.size() + 1 && C.k == (int)C.sel_col.size() && C.sel_off.back() == C.k);
   for (size_t i = 0; i < C.sel_cb.size(); ++i) {
     const int c = C.sel_cb[i];
-    REQUIRE(!C.cb_elim[c] && sel_row[c] < 0 && C.sel_off[i + 1] - C.sel_off[i] == C.cb_size[c]);
+    REQUIRE(!C.cb_elim[c] && sel_row[c] < 0 && C.sel_off[i + 1] - C.sel_off[i] == C.cols.cb_size[c]);
     sel_row[c] = C.sel_off[i];
-    for (int j = 0; j < C.cb_size[c]; ++j) REQUIRE(C.sel_col[C.sel_off[i] + j] == C.cb_red[c] + j && C.sel_col[C.sel_off[i] + j] < C.red_cols);
+    for (int j = 0; j < C.cols.cb_size[c]; ++j) REQUIRE(C.sel_col[C.sel_off[i] + j] == C.cb_red[c] + j && C.sel_col[C.sel_off[i] + j] < C.red_cols);
   }
   std::set<int> requested_e;
   REQUIRE(C.req_ea.size() == C.req_a.size() && C.req_eb.size() == C.req_a.size());
@@ -150,12 +150,12 @@ int verify(const Problem& p, const std::vector<std::pair<int, int>>& pairs, cons
       if (zero) { REQUIRE(row[t] == -1 && eb[t] == -1); continue; }
       const int c = cb_of[side[t]];
       if (C.cb_elim[c]) { REQUIRE(eb[t] == C.cb_red[c] && row[t] >= 0); requested_e.insert(eb[t]); }
-      else REQUIRE(eb[t] == -1 && row[t] == sel_row[c] && row[t] >= 0 && row[t] + C.cb_size[c] <= C.k);
+      else REQUIRE(eb[t] == -1 && row[t] == sel_row[c] && row[t] >= 0 && row[t] + C.cols.cb_size[c] <= C.k);
     }
   }
   for (e = 0; e < nE; ++e)
     for (int k = C.ew_begin[e]; k < C.ew_begin[e + 1]; ++k) {
-      if (requested_e.count(e)) REQUIRE(C.ew_sel[k] == sel_row[C.ew_g[k]] && C.ew_sel[k] >= 0 && C.ew_sel[k] + C.cb_size[C.ew_g[k]] <= C.k);
+      if (requested_e.count(e)) REQUIRE(C.ew_sel[k] == sel_row[C.ew_g[k]] && C.ew_sel[k] >= 0 && C.ew_sel[k] + C.cols.cb_size[C.ew_g[k]] <= C.k);
       else REQUIRE(C.ew_sel[k] == -1);
     }
   return 0;
@@ -176,10 +176,10 @@ int main() {
     REQUIRE(covariance_plan_build(B.p, pairs, &C, &why, true) == SK_OK);
     REQUIRE(verify(B.p, pairs, C) == 0);
     int hub_cb = -1;
-    for (size_t c = 0; c < C.cb_block.size(); ++c) if (C.cb_block[c] == blk(hub)) hub_cb = (int)c;
+    for (size_t c = 0; c < C.cols.cb_block.size(); ++c) if (C.cols.cb_block[c] == blk(hub)) hub_cb = (int)c;
     REQUIRE(hub_cb >= 0 && !C.cb_elim[hub_cb]);   // the hub has the most neighbours: visited last, and a neighbour has joined
-    printf("covariance_schur_plan_check chain ok: %d columns, %d eliminated blocks, %d reduced columns, %lld Schur terms, %zu parts, k = %d\n", C.num_cols, C.num_elim,
-           C.red_cols, C.schur_terms, C.spart_pair.size(), C.k);
+    printf("covariance_schur_plan_check chain ok: %d columns, %d eliminated blocks, %d reduced columns, %lld Schur terms, %zu parts, k = %d\n", C.cols.num_cols, C.num_elim,
+           C.red_cols, C.schur_terms, C.schur_parts.owner.size(), C.k);
   }
   {  // a bundle-adjustment shape: 5 cameras of 9, 400 points of 3, three observations per point, one pair observed twice
     const int ncam = 5, npt = 400;
@@ -198,8 +198,8 @@ int main() {
     REQUIRE(covariance_plan_build(B.p, pairs, &C, &why, true) == SK_OK);
     REQUIRE(verify(B.p, pairs, C) == 0);
     REQUIRE(C.num_elim == npt + 1 && C.red_cols == 9 * 3 + 6);   // the points and the block that nothing names
-    REQUIRE(!C.slong_pair.empty() && C.num_spartials > 0);       // two cameras share more than 64 points
-    printf("covariance_schur_plan_check bundle-adjustment shape ok: %d columns, %d eliminated blocks, %d reduced columns, %lld Schur terms, k = %d\n", C.num_cols,
+    REQUIRE(!C.schur_parts.long_owner.empty() && C.schur_parts.num_partials > 0);       // two cameras share more than 64 points
+    printf("covariance_schur_plan_check bundle-adjustment shape ok: %d columns, %d eliminated blocks, %d reduced columns, %lld Schur terms, k = %d\n", C.cols.num_cols,
            C.num_elim, C.red_cols, C.schur_terms, C.k);
   }
   {  // a landmark: 150 cameras, 400 points in windows of 4, point 400 seen by every camera
@@ -215,9 +215,9 @@ int main() {
     REQUIRE(covariance_plan_build(B.p, pairs, &C, &why, true) == SK_OK);
     REQUIRE(verify(B.p, pairs, C) == 0);
     REQUIRE(C.num_elim == npt && C.red_cols == 9 * (ncam - 2) && C.k == 9 * (ncam - 2));   // the landmark selects every moving camera
-    REQUIRE(!C.long_pair.empty());   // the landmark's own (e, e) pair: 150 terms
-    printf("covariance_schur_plan_check landmark ok: %d columns, %d reduced columns, %lld Schur terms, %zu long Schur pairs, %d partial tiles, k = %d\n", C.num_cols,
-           C.red_cols, C.schur_terms, C.slong_pair.size(), C.num_spartials, C.k);
+    REQUIRE(!C.pair_parts.long_owner.empty());   // the landmark's own (e, e) pair: 150 terms
+    printf("covariance_schur_plan_check landmark ok: %d columns, %d reduced columns, %lld Schur terms, %zu long Schur pairs, %d partial tiles, k = %d\n", C.cols.num_cols,
+           C.red_cols, C.schur_terms, C.schur_parts.long_owner.size(), C.schur_parts.num_partials, C.k);
   }
   {  // refusals: the column cap counts what is left; the default's message points at the setter
     Builder B(16 * 2049);
