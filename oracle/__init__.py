@@ -100,6 +100,8 @@ def lib():
         L.or_bal_reduced_system.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, dp, C.c_int, dp, dp]
         L.or_rotation_apply.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp]
         L.or_loss_evaluate.argtypes = [dp, C.c_int, C.c_double, dp]
+        L.or_loss_correct.argtypes = [dp, C.c_int, C.c_int, dp, C.c_int, dp]
+        L.or_loss_correct.restype = C.c_double
         L.or_solve_loss.argtypes = [C.c_int, ip, dp, C.c_int, ip, dp, ip, ip, ip, dp, ip,
                                     C.POINTER(Options), C.POINTER(Summary)]
         L.or_solve_bal_loss.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip, dp, dp, C.c_int, dp,
@@ -212,6 +214,17 @@ def loss_evaluate(loss, s):
     rho = np.zeros(3)
     lib().or_loss_evaluate(_dp(arr), root, float(s), _dp(rho))
     return rho
+
+
+def loss_correct(loss, r, J):
+    """The corrector on one residual block: (corrected residuals, corrected Jacobian, rho(|r|^2)) of r [k], J [k, n]."""
+    nodes = []
+    root = _flatten_loss(loss, nodes)
+    arr = np.asarray(nodes if nodes else [[0.0] * 5], dtype=np.float64)
+    r = np.array(r, dtype=np.float64)
+    J = np.array(J, dtype=np.float64, order="C")
+    rho = lib().or_loss_correct(_dp(arr), root, len(r), _dp(r), J.shape[1], _dp(J))
+    return r, J, rho
 
 
 def solve(block_sizes, x0, residual_blocks, options=None):

@@ -819,6 +819,9 @@ int or_rotation_apply(int op, int row_major, int jet_dim, const double* in, int 
 }
 
 void or_loss_evaluate(const double* loss_nodes, int root, double s, double* rho) { oracle::loss_evaluate(loss_nodes, root, s, rho); }
+double or_loss_correct(const double* loss_nodes, int root, int nres, double* res, int ncols, double* jac) {
+  return oracle::loss_correct(loss_nodes, root, nres, res, 1, &ncols, jac ? &jac : nullptr);
+}
 
 int or_solve_bal_loss(int C, int P, int N, const int* cam_idx, const int* pt_idx, const double* obs,
                       const double* loss_nodes, int loss_root, double* x, const or_options* opt, or_summary* summary) {

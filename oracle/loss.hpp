@@ -11,7 +11,8 @@
 // ceres::internal::Corrector.  PARITY UNPINNED against a Ceres build; pinned
 // instead by closed forms, finite differences and SciPy's least_squares
 // (loss = 'huber' / 'soft_l1' / 'cauchy' are the same functions), see
-// tests/test_oracle_loss.py.
+// tests/test_oracle_loss.py, and held to sympy derivatives of rho(s) at 60 digits
+// and more by tests/leaf_reference.py (tests/test_leaf_reference_cpu.py).
 #pragma once
 #include <cmath>
 #include <limits>
@@ -40,29 +41,31 @@ inline void loss_evaluate(const double* nodes, int id, double s, double rho[3]) 
     }
     case kSoftLOneLoss: {  // rho(s) = 2 a^2 (sqrt(1 + s / a^2) - 1)
       const double a2 = a * a, sum = 1.0 + s / a2, root = std::sqrt(sum);
-      rho[0] = 2.0 * a2 * (root - 1.0); rho[1] = std::max(tiny, 1.0 / root); rho[2] = -((1.0 / a2) * rho[1]) / (2.0 * sum);
+      rho[0] = 2.0 * s / (root + 1.0); rho[1] = std::max(tiny, 1.0 / root); rho[2] = -((1.0 / a2) * rho[1]) / (2.0 * sum);
       return;
     }
     case kCauchyLoss: {  // rho(s) = a^2 log(1 + s / a^2)
       const double a2 = a * a, c = 1.0 / a2, sum = 1.0 + s * c, inv = 1.0 / sum;
-      rho[0] = a2 * std::log(sum); rho[1] = std::max(tiny, inv); rho[2] = -c * (inv * inv);
+      rho[0] = a2 * std::log1p(s * c); rho[1] = std::max(tiny, inv); rho[2] = -c * (inv * inv);
       return;
     }
     case kTukeyLoss: {  // rho(s) = a^2/6 (1 - (1 - s/a^2)^3) for s <= a^2, a^2/6 beyond  (Ceres 1.x scaling)
       const double a2 = a * a;
       if (s <= a2) {
-        const double v = 1.0 - s / a2, v2 = v * v;
-        rho[0] = a2 / 6.0 * (1.0 - v2 * v); rho[1] = 0.5 * v2; rho[2] = -1.0 / a2 * v;
+        const double w = s / a2, v = 1.0 - w, v2 = v * v;
+        rho[0] = a2 / 6.0 * (w * (3.0 - 3.0 * w + w * w)); rho[1] = 0.5 * v2; rho[2] = -1.0 / a2 * v;
       } else { rho[0] = a2 / 6.0; rho[1] = 0.0; rho[2] = 0.0; }
       return;
     }
     case kTolerantLoss: {  // rho(s) = b log(1 + exp((s - a) / b)) - b log(1 + exp(-a / b))
-      const double c = b * std::log(1.0 + std::exp(-a / b));
+      const double k = std::exp(-a / b);
+      const double c = b * std::log1p(k);
       const double x = (s - a) / b;
       if (x > 36.7) { rho[0] = s - a - c; rho[1] = 1.0; rho[2] = 0.0; }
       else {
         const double ex = std::exp(x);
-        rho[0] = b * std::log(1.0 + ex) - c; rho[1] = std::max(tiny, ex / (1.0 + ex)); rho[2] = 0.5 / (b * (1.0 + std::cosh(x)));
+        const double t = s < b ? k * std::expm1(s / b) : ex - k;  // e^x - k, without cancellation at small s
+        rho[0] = b * std::log1p(t / (1.0 + k)); rho[1] = std::max(tiny, ex / (1.0 + ex)); rho[2] = 0.5 / (b * (1.0 + std::cosh(x)));
       }
       return;
     }

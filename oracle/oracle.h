@@ -58,6 +58,8 @@ int or_solve_bal(int C, int P, int N, const int* cam_idx, const int* pt_idx, con
 int or_rotation_apply(int op, int row_major, int jet_dim, const double* in, int n, double* out);
 /* robust losses (oracle/loss.hpp): nodes of 5 doubles {type, a, b, f, g} */
 void or_loss_evaluate(const double* loss_nodes, int root, double s, double* rho);
+/* The corrector in place on one residual block: res[nres], jac row-major nres x ncols (may be null); returns rho(|res|^2). */
+double or_loss_correct(const double* loss_nodes, int root, int nres, double* res, int ncols, double* jac);
 int or_solve_loss(int num_blocks, const int* block_sizes, double* x, int num_res_blocks,
                   const int* functor_ids, const double* consts, const int* const_off, const int* pidx,
                   const int* pidx_off, const double* loss_nodes, const int* block_loss,

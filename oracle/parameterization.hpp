@@ -3,7 +3,8 @@
 // for Problem::SetParameterBlockConstant.  Ceres is an un-vendored dependency of the reference: restated from the
 // published contracts (local_parameterization.h/.cc, householder_vector.h of Ceres 1.12-1.14); PARITY UNPINNED — the
 // reference holds no test or fixture for them.  tests/ additionally check every Jacobian against central differences
-// of Plus, which is independent of both this file and the device code.
+// of Plus, which is independent of both this file and the device code, and hold Plus and its Jacobian to the definitions
+// in mpmath (tests/leaf_reference.py, tests/test_leaf_reference_cpu.py).
 //
 // Written matrix-first (explicit Householder matrix, explicit quaternion product), unlike the device code's
 // in-register loops: two routes to the same numbers.
@@ -43,7 +44,8 @@ inline std::vector<double> householder_matrix(const double* x, int n) {
   for (int i = 0; i + 1 < n; ++i) sigma += x[i] * x[i];
   v[n - 1] = 1.0;
   const double pivot = x[n - 1];
-  if (sigma <= 2.220446049250313e-16) {
+  if (sigma <= 3.872591914849318e-121 * (pivot * pivot)) {  // 2^-400, relative: see csrc/parameterization.hpp
+    for (int i = 0; i + 1 < n; ++i) v[i] = 0.0;  // v = e_n: H = I or I - 2 e_n e_n^T whatever the scale of x
     if (pivot < 0.0) beta = 2.0;
   } else {
     const double mu = std::sqrt(pivot * pivot + sigma);

@@ -40,7 +40,8 @@ inline void quaternionToAngleAxis(const T* quaternion, T* angleAxis) {
     const T k = twoTheta / sinTheta;
     angleAxis[0] = q1 * k; angleAxis[1] = q2 * k; angleAxis[2] = q3 * k;
   } else {
-    angleAxis[0] = q1 * 2.0; angleAxis[1] = q2 * 2.0; angleAxis[2] = q3 * 2.0;
+    const double k = realPart(quaternion[0]) < 0.0 ? -2.0 : 2.0;  // w < 0: -q is the short way round here too
+    angleAxis[0] = q1 * k; angleAxis[1] = q2 * k; angleAxis[2] = q3 * k;
   }
 }
 

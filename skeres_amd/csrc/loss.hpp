@@ -7,8 +7,11 @@
 // Problem.addResidualBlock (CORE/Problem.scala:20-27; EX/RobustCurveFitting.scala:107).
 // Ceres itself is not vendored in the reference, so the formulas below restate
 // the published ceres::LossFunction::Evaluate contracts (rho, rho', rho'') of
-// Ceres 1.x and its Corrector (Triggs et al.): recalled, unverified against a
-// Ceres build — see DESIGN.md §2.
+// Ceres 1.x and its Corrector (Triggs et al.).  Not compared with a Ceres build;
+// verified by tests/leaf_reference.py: rho against its definition, rho' and rho''
+// against sympy derivatives of that rho, the corrector against its two defining
+// properties.  The values rho[0] are formed without the
+// cancellation the textbook forms have at small s.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "problem.hpp"  // LossType, LossNode
@@ -36,7 +39,7 @@ __host__ __device__ inline void loss_leaf(const LossNode& n, double s, double rh
     case kLossSoftLOne: {
       const double b = n.a * n.a, c = 1.0 / b;
       const double sum = 1.0 + s * c, tmp = sqrt(sum);
-      rho[0] = 2.0 * b * (tmp - 1.0);
+      rho[0] = 2.0 * s / (tmp + 1.0);  // = 2 b (tmp - 1) without the cancellation at small s
       rho[1] = loss_max(kLossMinPositive, 1.0 / tmp);
       rho[2] = -(c * rho[1]) / (2.0 * sum);
       return;
@@ -44,7 +47,7 @@ __host__ __device__ inline void loss_leaf(const LossNode& n, double s, double rh
     case kLossCauchy: {
       const double b = n.a * n.a, c = 1.0 / b;
       const double sum = 1.0 + s * c, inv = 1.0 / sum;
-      rho[0] = b * log(sum);
+      rho[0] = b * log1p(s * c);
       rho[1] = loss_max(kLossMinPositive, inv);
       rho[2] = -c * (inv * inv);
       return;
@@ -52,8 +55,8 @@ __host__ __device__ inline void loss_leaf(const LossNode& n, double s, double rh
     case kLossTukey: {
       const double a2 = n.a * n.a;
       if (s <= a2) {
-        const double v = 1.0 - s / a2, v2 = v * v;
-        rho[0] = a2 / 6.0 * (1.0 - v2 * v);
+        const double w = s / a2, v = 1.0 - w, v2 = v * v;
+        rho[0] = a2 / 6.0 * (w * (3.0 - 3.0 * w + w * w));  // = a^2/6 (1 - v^3), expanded: no cancellation at small s
         rho[1] = 0.5 * v2;
         rho[2] = -1.0 / a2 * v;
       } else { rho[0] = a2 / 6.0; rho[1] = 0.0; rho[2] = 0.0; }
@@ -61,13 +64,16 @@ __host__ __device__ inline void loss_leaf(const LossNode& n, double s, double rh
     }
     case kLossTolerant: {
       const double a = n.a, b = n.b;
-      const double c = b * log(1.0 + exp(-a / b));
+      const double k = exp(-a / b);
+      const double c = b * log1p(k);
       const double x = (s - a) / b;
       const double kLog2Pow53 = 36.7;  // ln(2^53): beyond it exp(x) swamps the 1
       if (x > kLog2Pow53) { rho[0] = s - a - c; rho[1] = 1.0; rho[2] = 0.0; }
       else {
         const double ex = exp(x);
-        rho[0] = b * log(1.0 + ex) - c;
+        // (1 + e^x) / (1 + k) = 1 + t / (1 + k), t = e^x - k = k expm1(s / b): rho(0) = 0 exactly and no difference of logs
+        const double t = s < b ? k * expm1(s / b) : ex - k;
+        rho[0] = b * log1p(t / (1.0 + k));
         rho[1] = loss_max(kLossMinPositive, ex / (1.0 + ex));
         rho[2] = 0.5 / (b * (1.0 + cosh(x)));
       }

@@ -4,7 +4,8 @@
 // identity, subset, quaternion, homogeneousVector) for ceres::Problem::AddParameterBlock / SetParameterization, which
 // its Problem inherits (CORE/Problem.scala:16).  Ceres itself is not vendored in the reference, so the formulas below
 // restate the published ceres::LocalParameterization contracts of Ceres 1.x (local_parameterization.cc,
-// internal/ceres/householder_vector.h): recalled, unverified against a Ceres build — DESIGN.md section 2.
+// internal/ceres/householder_vector.h).  Not compared with a Ceres build; Plus and its Jacobian are verified against the
+// definitions (exp(delta) (x) x; |x| H(x) y(delta) with the exact reflection) by tests/leaf_reference.py — DESIGN.md section 2.
 // A constant parameter block (Problem::SetParameterBlockConstant) is kParamConstant: local size 0.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 
 namespace sk {
 
+constexpr double kHouseholderPole = 3.872591914849318e-121;  // 2^-400
 constexpr int kParamMaxSize = 16;  // global size of a parameterized block (the Jacobian lives in registers / on the stack)
 
 // One parameter block's parameterization, flattened for the device: `constant_mask` bit i set = coordinate i is held
@@ -30,7 +32,16 @@ __host__ __device__ inline void householder_vector(const double* x, int n, doubl
   v[n - 1] = 1.0;
   *beta = 0.0;
   const double x_pivot = x[n - 1];
-  if (sigma <= 2.220446049250313e-16) {
+  // x = +-|x| e_n to working precision: H = I, or I - 2 e_n e_n^T for a negative pivot.  The test is relative, a homogeneous
+  // vector has no scale, and the bound is kHouseholderPole = 2^-400, not Ceres' absolute ulp(1): next to the pole the exact
+  // reflection is I - 2 h h^T / |h|^2 (h = x's head), an O(1) step away from I, and the general branch below computes it to a
+  // few ulp (v_pivot = -sigma / (x_pivot + mu) has no cancellation, |v[i]| <= 2 / sqrt(sigma / x_pivot^2) <= 2^201,
+  // beta v[i] v[j] <= 2) as long as v_pivot^2 = (sigma / (2 x_pivot))^2 is a normal number: with sigma >= 2^-400 x_pivot^2
+  // that is |x_pivot| >= 2^-110 (7.7e-34).  Below that size AND within 2^-200 of the pole, v_pivot^2 underflows, beta becomes 0
+  // and H = I again, the same O(1) change of chart; no caller has homogeneous vectors of 1e-34.  With x_pivot = 0 only
+  // sigma = 0 comes here.
+  if (sigma <= kHouseholderPole * (x_pivot * x_pivot)) {
+    for (int i = 0; i < n - 1; ++i) v[i] = 0.0;
     if (x_pivot < 0.0) *beta = 2.0;
     return;
   }

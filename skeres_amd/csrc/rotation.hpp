@@ -43,7 +43,11 @@ SK_HD void quaternion_to_angle_axis(const T* q, T* aa) {
     const T k = two_theta / sin_theta;
     aa[0] = q1 * k; aa[1] = q2 * k; aa[2] = q3 * k;
   } else {
-    aa[0] = q1 * 2.0; aa[1] = q2 * 2.0; aa[2] = q3 * 2.0;
+    // w < 0: the same rotation the short way round is -q, as above.  The reference (and ceres/rotation.h) return 2 (q1, q2, q3)
+    // whatever the sign of w: values wrong by at most the 1e-162 at which sin^2 underflows, derivatives by their sign
+    // 
+    const double k = jneg(q[0]) ? -2.0 : 2.0;
+    aa[0] = q1 * k; aa[1] = q2 * k; aa[2] = q3 * k;
   }
 }
 
