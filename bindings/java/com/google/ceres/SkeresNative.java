@@ -144,6 +144,7 @@ public final class SkeresNative {
   public static native int skOptionsSetEta(long o, double v);
   public static native int skOptionsSetMaxLinearSolverIterations(long o, int v);
   public static native int skOptionsSetMinLinearSolverIterations(long o, int v);
+  public static native int skOptionsSetSchurElimination(long o, int v);
   public static native int skOptionsSetCholeskyEnvelope(long o, int v);
   public static native int skOptionsSetCholeskyDissection(long o, int v);
   public static native int skOptionsSetCholeskyBorder(long o, int v);

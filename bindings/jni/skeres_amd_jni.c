@@ -318,6 +318,7 @@ SK_OPT_INT(skOptionsSetPreconditionerType, sk_options_set_preconditioner_type)
 SK_OPT_DBL(skOptionsSetEta, sk_options_set_eta)
 SK_OPT_INT(skOptionsSetMaxLinearSolverIterations, sk_options_set_max_linear_solver_iterations)
 SK_OPT_INT(skOptionsSetMinLinearSolverIterations, sk_options_set_min_linear_solver_iterations)
+SK_OPT_INT(skOptionsSetSchurElimination, sk_options_set_schur_elimination)
 SK_OPT_INT(skOptionsSetCholeskyEnvelope, sk_options_set_cholesky_envelope)
 SK_OPT_INT(skOptionsSetCholeskyDissection, sk_options_set_cholesky_dissection)
 SK_OPT_INT(skOptionsSetCholeskyBorder, sk_options_set_cholesky_border)

@@ -283,6 +283,8 @@ object Solver {
     // MI355X additions (no counterpart in ceres::Solver::Options)
     def setDevice(hipDevice: Int): Unit = SkeresNative.skOptionsSetDevice(handle, hipDevice)
     def setDistributionMode(mode: Int): Unit = SkeresNative.skOptionsSetDistributionMode(handle, mode)
+    /** CGNR: conjugate gradients on the implicit Schur complement of an independent set of parameter blocks (default off) */
+    def setSchurElimination(on: Boolean): Unit = SkeresNative.skOptionsSetSchurElimination(handle, if (on) 1 else 0)
     /** this JVM is rank `rank` of `world`, one per GPU; the collective is the library's own RCCL all-reduce */
     def setDistributedRccl(rank: Int, world: Int, uniqueId: Array[Byte]): Unit = {
       rccl = SkeresNative.skAllreduceRcclInit(rank, world, uniqueId)

@@ -479,7 +479,8 @@ int sk_options_set_max_num_consecutive_invalid_steps(sk_options* o, int n);
  * JACOBI (the block diagonal of the matrix over the parameter blocks), eta 0.1, at most 500 and at least 0 iterations.
  * SK_ERR_INVALID_ARGUMENT: a preconditioner type other than the two, eta outside (0, 1), a negative count, min > max.
  * Taken: device functors and recorded functors, robust losses, constant blocks, the four local parameterizations,
- * bundle-adjustment-shaped problems (as the full camera + point system).  Refused with SK_ERR_UNSUPPORTED when the solver is
+ * bundle-adjustment-shaped problems (as the full camera + point system, or with sk_options_set_schur_elimination on the
+ * reduced camera system).  Refused with SK_ERR_UNSUPPORTED when the solver is
  * created: host-evaluated (director) residual blocks, a parameter block of tangent size above 16, DOGLEG, parameter bounds, a
  * world of more than one rank, dense-row problems.  sk_options_set_cholesky_tuning has no effect.  The iteration is enqueued
  * launch by launch (sk_solver_stat "graph_replay" is 0); the step does not depend on how many CG iterations are enqueued
@@ -488,6 +489,21 @@ int sk_options_set_preconditioner_type(sk_options* o, int type);
 int sk_options_set_eta(sk_options* o, double eta);
 int sk_options_set_max_linear_solver_iterations(sk_options* o, int n);
 int sk_options_set_min_linear_solver_iterations(sk_options* o, int n);
+/* (no reference counterpart) CGNR on the implicit Schur complement.  Default 0.  on != 0, under SK_CGNR only (no effect under the
+ * other solver types): an independent set E of the moving parameter blocks is eliminated (the greedy rule of
+ * sk_covariance_options_set_schur_elimination: a bundle-adjustment problem's points), and the same conjugate-gradient loop solves
+ * S y_F = s with S = U - W V^-1 W^T over the kept blocks F, applied as S v = J_F^T (I - J_E V^-1 J_E^T) J_F v + D_F^2 v and never
+ * formed; then y_E = V^-1 (b_E - W^T y_F).  SK_JACOBI is then the block diagonal of S (Ceres' SCHUR_JACOBI), SK_IDENTITY none.
+ * When every moving block is in E the step is the back-substitution alone: 0 CG iterations, status 0.  Accepts and refuses what
+ * CGNR does.  sk_solver_stat: "schur_elimination" (0 or 1), "eliminated_blocks", "reduced_columns" (the columns CG runs on),
+ * "schur_diagonal_pairs" (the (F block, e-block) pairs that the block diagonal of S sums over); the full report names the
+ * elimination and the two counts when the option is on. */
+int sk_options_set_schur_elimination(sk_options* o, int on);
+/* (no reference counterpart) the elimination of sk_options_set_schur_elimination for this problem, from host data alone (no
+ * device): eliminated_of_block [parameter blocks]: 1 in E, 0 in F, -1 constant / no columns; the number of blocks in E, the columns
+ * of F, the e-blocks on more than 64 residual blocks (summed in two launches) and the (F block, e-block) pairs.  Any pointer may be
+ * NULL.  SK_ERR_UNSUPPORTED as a CGNR solver on one rank with LEVENBERG_MARQUARDT refuses the problem. */
+int sk_cgnr_elimination_plan(const sk_problem* p, int* eliminated_of_block, int* num_eliminated, int* reduced_columns, int* long_eliminated_blocks, int* fe_pairs);
 /* MI355X-side knobs (no reference counterpart) */
 int sk_options_set_device(sk_options* o, int hip_device);             /* default: current device */
 int sk_options_set_stream(sk_options* o, void* hip_stream);           /* default: a private stream */
@@ -719,7 +735,9 @@ int sk_solver_distribution(const sk_solver* s, double* allreduce_seconds, double
  * CGNR:
  *   "cg_iterations" CG iterations since the solver was created, "cg_iterations_last" of the last linear solve,
  *   "cg_status_last" how it ended (0 the stopping test, 1 the iteration limit, 2 breakdown, 3 zero right-hand side; -1 before
- *   the first), "cg_batches" reads of the done flag, "jacobian_nonzeros" stored entries of the block-sparse Jacobian
+ *   the first), "cg_batches" reads of the done flag, "jacobian_nonzeros" stored entries of the block-sparse Jacobian,
+ *   "schur_elimination" (0 or 1), "eliminated_blocks", "reduced_columns" (all columns without the elimination),
+ *   "schur_diagonal_pairs": sk_options_set_schur_elimination
  * dense rows (DENSE_NORMAL_CHOLESKY over one parameter block):
  *   "jtj_flops_algorithmic" m n (n + 1): SURVEY.md section 8(d)'s figure for J^T J (sk_solver_syrk_flops_per_solve counts
  *                           the padded 128 x 128 tiles the launch computes) */

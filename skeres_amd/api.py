@@ -121,6 +121,8 @@ _SIGS = {
     "sk_options_set_max_linear_solver_iterations": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_options_set_min_linear_solver_iterations": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_options_set_cholesky_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "sk_options_set_schur_elimination": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_cgnr_elimination_plan": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _ip, _ip]),
     "sk_options_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sk_options_set_distributed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ALLREDUCE_FN, C.c_void_p]),
     "sk_options_set_reduce_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -1409,6 +1411,18 @@ class Covariance:
 
 
 class Solver:
+    @staticmethod
+    def cgnrEliminationPlan(problem):
+        """The elimination of Options.setSchurElimination for this problem, from host data alone (sk_cgnr_elimination_plan): a dict
+        with eliminated_of_block (per parameter block: 1 in E, 0 in F, -1 constant / no columns), num_eliminated, reduced_columns,
+        long_eliminated_blocks and fe_pairs."""
+        nb = lib().sk_problem_num_parameter_blocks(problem._h)
+        of_block = np.zeros(max(nb, 1), dtype=np.int32)
+        n, cols, long_e, pairs = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _check(lib().sk_cgnr_elimination_plan(problem._h, of_block.ctypes.data_as(_ip), C.byref(n), C.byref(cols), C.byref(long_e), C.byref(pairs)))
+        return dict(eliminated_of_block=of_block[:nb].copy(), num_eliminated=n.value, reduced_columns=cols.value,
+                    long_eliminated_blocks=long_e.value, fe_pairs=pairs.value)
+
     class Options:
         def __init__(self):
             self._h = lib().sk_options_new()
@@ -1450,6 +1464,11 @@ class Solver:
         def setEta(self, v): self._set("eta", float(v))
         def setMaxLinearSolverIterations(self, n): self._set("max_linear_solver_iterations", int(n))
         def setMinLinearSolverIterations(self, n): self._set("min_linear_solver_iterations", int(n))
+
+        def setSchurElimination(self, on):
+            """CGNR: conjugate gradients on the implicit Schur complement of an independent set of parameter blocks (default off;
+            no effect under the other solver types).  JACOBI is then the block diagonal of the Schur complement."""
+            _check(lib().sk_options_set_schur_elimination(self._h, int(bool(on))))
 
         def setCholeskyTuning(self, group=0, lookahead=True):
             _check(lib().sk_options_set_cholesky_tuning(self._h, int(group), int(bool(lookahead))))

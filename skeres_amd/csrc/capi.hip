@@ -789,6 +789,30 @@ int sk_options_set_preconditioner_type(sk_options* o, int t) {
   if (t != SK_IDENTITY && t != SK_JACOBI) { set_error("invalid preconditioner type %d (IDENTITY and JACOBI are implemented)", t); return SK_ERR_INVALID_ARGUMENT; }
   o->o.preconditioner_type = t; return SK_OK;
 }
+int sk_options_set_schur_elimination(sk_options* o, int on) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.cgnr_schur_elimination = on != 0; return SK_OK;
+}
+int sk_cgnr_elimination_plan(const sk_problem* p, int* eliminated_of_block, int* num_eliminated, int* reduced_columns, int* long_eliminated_blocks, int* fe_pairs) {
+  SK_GUARD_BEGIN
+  if (!p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  const std::string refusal = cgnr_refusal(p->p, 1, false);
+  if (!refusal.empty()) { set_error("%s", refusal.c_str()); return SK_ERR_UNSUPPORTED; }
+  CgnrPlan plan;
+  std::string why;
+  const int rc = cgnr_plan_build(p->p, &plan, &why, /*schur_elimination*/ true);
+  if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
+  if (eliminated_of_block) {
+    for (size_t b = 0; b < p->p.block_ptr.size(); ++b) eliminated_of_block[b] = -1;
+    for (size_t c = 0; c < plan.cols.cb_block.size(); ++c) eliminated_of_block[plan.cols.cb_block[c]] = plan.cb_elim[c];
+  }
+  if (num_eliminated) *num_eliminated = (int)plan.E.cb.size();
+  if (reduced_columns) *reduced_columns = plan.reduced_cols;
+  if (long_eliminated_blocks) *long_eliminated_blocks = (int)plan.E.parts.long_owner.size();
+  if (fe_pairs) *fe_pairs = (int)plan.fp_e.size();
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
 int sk_options_set_eta(sk_options* o, double v) {
   if (!(v > 0.0 && v < 1.0)) { set_error("eta must lie inside (0, 1)"); return SK_ERR_INVALID_ARGUMENT; }
   o->o.eta = v; return SK_OK;
@@ -896,7 +920,7 @@ static std::unique_ptr<SolverBase> make_solver(const Options& o, Problem* p, int
     set_error("local parameterizations and constant parameter blocks are implemented for residual-block problems (DENSE_QR / DENSE_NORMAL_CHOLESKY; identity, subset and constant blocks under DENSE_SCHUR), not for dense rows (not supported here)");
     *rc = SK_ERR_UNSUPPORTED; return nullptr;
   }
-  if (o.linear_solver_type == SK_CGNR) {  // every shape it takes, bundle adjustment included, as the full system: no elimination
+  if (o.linear_solver_type == SK_CGNR) {  // every shape it takes, bundle adjustment included: the full system, or the implicit Schur complement (sk_options_set_schur_elimination)
     const std::string refusal = cgnr_refusal(*p, o.world, o.trust_region_strategy_type == SK_DOGLEG);  // (host data alone: before any device is touched)
     if (!refusal.empty()) { set_error("%s", refusal.c_str()); *rc = SK_ERR_UNSUPPORTED; return nullptr; }
     return make_cgnr_solver(o, p);

@@ -1,5 +1,6 @@
 // HIP kernels of the CGNR solver (gfx950, wave64, fp64): the two products with the block-sparse Jacobian, the block sums and the
-// block-Jacobi preconditioner, the fused vector updates and the scalar kernels of the conjugate-gradient loop.  All of them stream
+// block-Jacobi preconditioner, the fused vector updates and the scalar kernels of the conjugate-gradient loop, and for the Schur
+// elimination the projection w - J_E V^-1 J_E^T w and the block diagonal of the Schur complement.  All of them stream
 // HBM; every sum runs in an order that the plan fixes (cgnr_plan.hpp), without floating-point atomics.  The kernels of the loop
 // read the done flag first and return when it is set, so the host may enqueue iterations ahead of what the device will need.
 #include <hip/hip_runtime.h>
@@ -125,7 +126,8 @@ void launch_cgnr_gradient_norms(const double* gs, const double* scale, int n, co
 // ---- the preconditioner's factors -------------------------------------------------------------------------------------------------
 // One lane per column block: D2 of its columns, and the Cholesky factor of its size x size matrix (size <= kCgnrMaxBlock) in the
 // lane's own memory, row-major lower triangle with the diagonal.
-__global__ __launch_bounds__(64) void cgnr_precond_factor_kernel(CgnrCols C, const double* bsum, double lo, double hi, double radius, double* D2, double* L, int* flags) {
+__global__ __launch_bounds__(64) void cgnr_precond_factor_kernel(CgnrCols C, const double* bsum, double lo, double hi, double radius, double* D2, double* L, int* flags,
+                                                                 const double* sub) {
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= C.num_cb) return;
   const int size = C.cb_size[c], col = C.cb_col[c];
@@ -135,6 +137,7 @@ __global__ __launch_bounds__(64) void cgnr_precond_factor_kernel(CgnrCols C, con
     const double d = fmin(fmax(m[j * size + j], lo), hi) / radius;
     D2[col + j] = d;
     if (L) for (int k = 0; k <= j; ++k) a[j * size + k] = m[j * size + k] + (k == j ? d : 0.0);
+    if (L && sub) for (int k = 0; k <= j; ++k) a[j * size + k] -= sub[C.cb_moff[c] + j * size + k];
   }
   if (!L) return;
   bool ok = true;
@@ -154,8 +157,9 @@ __global__ __launch_bounds__(64) void cgnr_precond_factor_kernel(CgnrCols C, con
   double* out = L + C.cb_moff[c];
   for (int j = 0; j < size; ++j) for (int k = 0; k <= j; ++k) out[j * size + k] = a[j * size + k];
 }
-void launch_cgnr_precond_factor(const CgnrCols& C, const double* bsum, double lo, double hi, double radius, double* D2, double* L, int* flags, hipStream_t s) {
-  if (C.num_cb > 0) hipLaunchKernelGGL(cgnr_precond_factor_kernel, dim3((C.num_cb + 63) / 64), dim3(64), 0, s, C, bsum, lo, hi, radius, D2, L, flags);
+void launch_cgnr_precond_factor(const CgnrCols& C, const double* bsum, double lo, double hi, double radius, double* D2, double* L, int* flags, hipStream_t s,
+                                const double* sub) {
+  if (C.num_cb > 0) hipLaunchKernelGGL(cgnr_precond_factor_kernel, dim3((C.num_cb + 63) / 64), dim3(64), 0, s, C, bsum, lo, hi, radius, D2, L, flags, sub);
 }
 
 // ---- w = J v ----------------------------------------------------------------------------------------------------------------------
@@ -194,6 +198,7 @@ __device__ inline void cgnr_jtw_finish(int mode, int col, int size, const double
     double v = acc[j];
     if (mode == kCgnrJtwCg) { const double pn = fma(beta, p[col + j], z[col + j]); p[col + j] = pn; v += D2[col + j] * pn; }
     else if (mode == kCgnrJtwVector) v += D2[col + j] * z[col + j];
+    else if (mode == kCgnrJtwNegated) v = -v;
     q[col + j] = v;
   }
 }
@@ -396,6 +401,173 @@ __global__ __launch_bounds__(256) void cgnr_scalar_end_kernel(const double* part
 }
 void launch_cgnr_scalar_end(const double* partials3, int nparts, double eta, int min_it, int max_it, double* scal, int* flags, hipStream_t s) {
   hipLaunchKernelGGL(cgnr_scalar_end_kernel, dim3(1), dim3(256), 0, s, partials3, nparts, eta, min_it, max_it, scal, flags);
+}
+
+// ---- the Schur elimination --------------------------------------------------------------------------------------------------------
+// w <- w - J_e V_e^-1 J_e^T w per e-block, the hot kernel of an application of S.  t = J_e^T w is summed as cgnr_jtw_kernel sums
+// it (kCgnrLanes lanes per part, the butterfly leaves the same bits in every lane); the lanes of a single-part block then each
+// solve with the block's factor and subtract J_e u from the rows of their own slots.  No other e-block has entries in those rows,
+// and every read of w by the group precedes the butterfly, so the stores need no atomics.  A long e-block leaves partial sums;
+// cgnr_eliminate_long_kernel adds them in part order, solves and subtracts over the block's whole slot list.
+__device__ inline void cgnr_eliminate_finish(int mode, const CgnrJac& J, const CgnrCols& E, int c, int begin, int end, int lane, double* t, const double* L,
+                                             const double* b, double* w, double* y) {
+  const int size = E.cb_size[c], col = E.cb_col[c];
+  const double* l = L + E.cb_moff[c];
+  if (mode == kCgnrElimBacksub) {
+#pragma unroll
+    for (int j = 0; j < kCgnrMaxBlock; ++j) if (j < size) t[j] = b[col + j] - t[j];
+  }
+#pragma unroll
+  for (int j = 0; j < kCgnrMaxBlock; ++j) {  // L u' = t
+    if (j >= size) continue;
+    double v = t[j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) v -= l[j * size + k] * t[k];
+    t[j] = v / l[j * size + j];
+  }
+#pragma unroll
+  for (int j = kCgnrMaxBlock - 1; j >= 0; --j) {  // L^T u = u'
+    if (j >= size) continue;
+    double v = t[j];
+#pragma unroll
+    for (int k = j + 1; k < kCgnrMaxBlock; ++k) if (k < size) v -= l[k * size + j] * t[k];
+    t[j] = v / l[j * size + j];
+  }
+  if (mode == kCgnrElimBacksub) {
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < kCgnrMaxBlock; ++j) if (j < size) y[col + j] = t[j];
+    }
+    return;
+  }
+  for (int k = begin + lane; k < end; k += kCgnrLanes) {
+    const int slot = E.cb_slots[k], i = J.slot_owner[slot];
+    // a residual block that names the e-block more than once: the first of its slots subtracts for all of them (one store per row)
+    bool first = true;
+    for (int o = J.slot_begin[i]; o < slot; ++o) if (J.slot_pos[o] >= 0 && J.slot_col[o] == col) first = false;
+    if (!first) continue;
+    const int row0 = J.row_off[i], nres = J.row_off[i + 1] - row0;
+    const int width = (J.val_off[i + 1] - J.val_off[i]) / nres;
+    for (int r = 0; r < nres; ++r) {
+      double s = 0.0;
+      for (int o = slot; o < J.slot_begin[i + 1]; ++o) {
+        if (J.slot_pos[o] < 0 || J.slot_col[o] != col) continue;
+        const double* v = J.values + J.val_off[i] + (size_t)r * width + J.slot_pos[o];
+#pragma unroll
+        for (int j = 0; j < kCgnrMaxBlock; ++j) if (j < size) s += v[j] * t[j];
+      }
+      w[row0 + r] -= s;
+    }
+  }
+}
+__global__ __launch_bounds__(64) void cgnr_eliminate_kernel(int mode, CgnrJac J, CgnrCols E, const double* L, const double* b, double* w, double* y, double* partial,
+                                                            const int* flags) {
+  if (cg_done(flags)) return;
+  const int sub = threadIdx.x / kCgnrLanes, lane = threadIdx.x % kCgnrLanes;
+  const int part = blockIdx.x * (64 / kCgnrLanes) + sub;
+  if (part >= E.num_parts) return;  // (a whole group of lanes leaves: the butterfly stays inside a group)
+  const int c = E.part_cb[part], size = E.cb_size[c], begin = E.part_begin[part], end = E.part_end[part], out = E.part_out[part];
+  double acc[kCgnrMaxBlock];
+#pragma unroll
+  for (int j = 0; j < kCgnrMaxBlock; ++j) acc[j] = 0.0;
+  for (int k = begin + lane; k < end; k += kCgnrLanes) {
+    const int slot = E.cb_slots[k], i = J.slot_owner[slot];
+    const int row0 = J.row_off[i], nres = J.row_off[i + 1] - row0;
+    const int width = (J.val_off[i + 1] - J.val_off[i]) / nres;
+    const double* v = J.values + J.val_off[i] + J.slot_pos[slot];
+    for (int r = 0; r < nres; ++r) {
+      const double wv = w[row0 + r];
+#pragma unroll
+      for (int j = 0; j < kCgnrMaxBlock; ++j) if (j < size) acc[j] += v[(size_t)r * width + j] * wv;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kCgnrMaxBlock; ++j)
+    for (int off = kCgnrLanes / 2; off > 0; off >>= 1) acc[j] += __shfl_xor(acc[j], off, kCgnrLanes);
+  if (out < 0) { cgnr_eliminate_finish(mode, J, E, c, begin, end, lane, acc, L, b, w, y); return; }
+  if (lane != 0) return;
+#pragma unroll
+  for (int j = 0; j < kCgnrMaxBlock; ++j) if (j < size) partial[(size_t)out * kCgnrLanes + j] = acc[j];
+}
+__global__ __launch_bounds__(64) void cgnr_eliminate_long_kernel(int mode, CgnrJac J, CgnrCols E, const int* long_slots, const double* L, const double* b, double* w,
+                                                                 double* y, const double* partial, const int* flags) {
+  if (cg_done(flags)) return;
+  const int sub = threadIdx.x / kCgnrLanes, lane = threadIdx.x % kCgnrLanes;
+  const int lb = blockIdx.x * (64 / kCgnrLanes) + sub;
+  if (lb >= E.num_long) return;
+  const int c = E.long_cb[lb], size = E.cb_size[c], begin = E.long_begin[lb], end = E.long_begin[lb + 1];
+  double acc[kCgnrMaxBlock];
+#pragma unroll
+  for (int j = 0; j < kCgnrMaxBlock; ++j) acc[j] = 0.0;
+  for (int k = begin + lane; k < end; k += kCgnrLanes) {
+#pragma unroll
+    for (int j = 0; j < kCgnrMaxBlock; ++j) if (j < size) acc[j] += partial[(size_t)k * kCgnrLanes + j];
+  }
+#pragma unroll
+  for (int j = 0; j < kCgnrMaxBlock; ++j)
+    for (int off = kCgnrLanes / 2; off > 0; off >>= 1) acc[j] += __shfl_xor(acc[j], off, kCgnrLanes);
+  cgnr_eliminate_finish(mode, J, E, c, long_slots[2 * lb], long_slots[2 * lb + 1], lane, acc, L, b, w, y);
+}
+void launch_cgnr_eliminate(int mode, const CgnrJac& J, const CgnrCols& E, const int* long_slots, const double* L, const double* b, double* w, double* y,
+                           double* partial, const int* flags, hipStream_t s) {
+  const int per = 64 / kCgnrLanes;
+  if (E.num_parts > 0) hipLaunchKernelGGL(cgnr_eliminate_kernel, dim3((E.num_parts + per - 1) / per), dim3(64), 0, s, mode, J, E, L, b, w, y, partial, flags);
+  if (E.num_long > 0) hipLaunchKernelGGL(cgnr_eliminate_long_kernel, dim3((E.num_long + per - 1) / per), dim3(64), 0, s, mode, J, E, long_slots, L, b, w, y, (const double*)partial, flags);
+}
+
+// The block diagonal of S, once per linear solve.  One wave per part of an F block's pair list, as cgnr_block_diag_kernel: lane e
+// (e, e + 64, ... below size^2) owns entry (a, b) and walks the part's pairs in plan order.  Per pair it forms rows a and b of
+// W_ge over the pair's terms, solves both with L_e and adds their product: redundant across the lanes of a row, but without a
+// hand-over between lanes, and the launch runs once where the projection runs every iteration.
+__global__ __launch_bounds__(64) void cgnr_schur_diag_kernel(CgnrJac J, CgnrCols F, CgnrPairs P, const double* L, double* sdiag, double* partial) {
+  const int part = blockIdx.x;
+  const int g = P.part_f[part], size = F.cb_size[g], begin = P.part_begin[part], end = P.part_end[part], out = P.part_out[part];
+  for (int e = threadIdx.x; e < size * size; e += 64) {
+    const int a = e / size, b = e - a * size;
+    double s = 0.0;
+    for (int q = begin; q < end; ++q) {
+      const int ce = P.pair_e[q], se = P.cb_size[ce];
+      const double* l = L + P.cb_moff[ce];
+      double xa[kCgnrMaxBlock], xb[kCgnrMaxBlock];
+#pragma unroll
+      for (int j = 0; j < kCgnrMaxBlock; ++j) xa[j] = xb[j] = 0.0;
+      for (int k = P.pair_slot_begin[q]; k < P.pair_slot_begin[q + 1]; ++k) {
+        const int sg = P.slot_g[k], sl = P.slot_e[k], i = J.slot_owner[sg];
+        const int nres = J.row_off[i + 1] - J.row_off[i];
+        const int width = (J.val_off[i + 1] - J.val_off[i]) / nres;
+        const double* vg = J.values + J.val_off[i] + J.slot_pos[sg];
+        const double* ve = J.values + J.val_off[i] + J.slot_pos[sl];
+        for (int r = 0; r < nres; ++r) {
+          const double ga = vg[(size_t)r * width + a], gb = vg[(size_t)r * width + b];
+#pragma unroll
+          for (int j = 0; j < kCgnrMaxBlock; ++j) if (j < se) { const double ev = ve[(size_t)r * width + j]; xa[j] += ev * ga; xb[j] += ev * gb; }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kCgnrMaxBlock; ++j) {  // L_e x = W_ge's row, twice
+        if (j >= se) continue;
+        double va = xa[j], vb = xb[j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) { va -= l[j * se + k] * xa[k]; vb -= l[j * se + k] * xb[k]; }
+        xa[j] = va / l[j * se + j]; xb[j] = vb / l[j * se + j];
+        s += xa[j] * xb[j];
+      }
+    }
+    if (out < 0) sdiag[F.cb_moff[g] + e] = s; else partial[(size_t)out * 256 + e] = s;
+  }
+}
+__global__ __launch_bounds__(64) void cgnr_schur_diag_long_kernel(CgnrCols F, CgnrPairs P, double* sdiag, const double* partial) {
+  const int g = P.long_f[blockIdx.x], size = F.cb_size[g];
+  const int begin = P.long_begin[blockIdx.x], end = P.long_begin[blockIdx.x + 1];
+  for (int e = threadIdx.x; e < size * size; e += 64) {
+    double s = 0.0;
+    for (int k = begin; k < end; ++k) s += partial[(size_t)k * 256 + e];
+    sdiag[F.cb_moff[g] + e] = s;
+  }
+}
+void launch_cgnr_schur_diag(const CgnrJac& J, const CgnrCols& F, const CgnrPairs& P, const double* L, double* sdiag, double* partial, hipStream_t s) {
+  if (P.num_parts > 0) hipLaunchKernelGGL(cgnr_schur_diag_kernel, dim3(P.num_parts), dim3(64), 0, s, J, F, P, L, sdiag, partial);
+  if (P.num_long > 0) hipLaunchKernelGGL(cgnr_schur_diag_long_kernel, dim3(P.num_long), dim3(64), 0, s, F, P, sdiag, (const double*)partial);
 }
 
 // ---- the candidate ----------------------------------------------------------------------------------------------------------------

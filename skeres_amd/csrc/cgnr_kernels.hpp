@@ -55,14 +55,17 @@ void launch_cgnr_scale_apply(const CgnrJac& J, const double* scale, hipStream_t 
 void launch_cgnr_gradient_norms(const double* gs, const double* scale, int n, const double* x, int ng, double* b, double* scal, hipStream_t s);
 
 // --- per linear solve --------------------------------------------------------------------------------------------------------------
-// D2 = clamp(diag bsum, lo, hi) / radius; JACOBI (L != null): L L^T = bsum + D2 per column block, flags[kCgFail] where that fails
-void launch_cgnr_precond_factor(const CgnrCols& C, const double* bsum, double lo, double hi, double radius, double* D2, double* L, int* flags, hipStream_t s);
+// D2 = clamp(diag bsum, lo, hi) / radius; JACOBI (L != null): L L^T = bsum + D2 (- sub, in bsum's layout, when given) per column
+// block, flags[kCgFail] where that fails
+void launch_cgnr_precond_factor(const CgnrCols& C, const double* bsum, double lo, double hi, double radius, double* D2, double* L, int* flags, hipStream_t s,
+                                const double* sub = nullptr);
 
 // w = J v.  v = fma(beta, p, z) with beta = scal[kCgBeta] (p != null), else v = z.  flags (may be null): the done flag.
 void launch_cgnr_jp(const CgnrJac& J, const double* z, const double* p, const double* scal, double* w, const int* flags, hipStream_t s);
 // q = J^T w (+ D2 v).  kCgnrJtwCg: v = p <- fma(beta, p, z), written by the launch that owns the block; kCgnrJtwVector: v = z as
 // it is; kCgnrJtwPlain: no vector, no D2.  partial: [num_partials * kCgnrLanes]
-enum { kCgnrJtwCg = 0, kCgnrJtwVector = 1, kCgnrJtwPlain = 2 };
+// kCgnrJtwNegated: q = -J^T w.
+enum { kCgnrJtwCg = 0, kCgnrJtwVector = 1, kCgnrJtwPlain = 2, kCgnrJtwNegated = 3 };
 void launch_cgnr_jtw(int mode, const CgnrJac& J, const CgnrCols& C, const double* w, const double* D2, const double* z, double* p, const double* scal,
                      double* q, double* partial, const int* flags, hipStream_t s);
 // partials[chunk] = sum a_i b_i (kind 0) or sum a_i (b_i + a_i / 2) (kind 1) over chunks of kCgnrDotChunk
@@ -81,6 +84,28 @@ void launch_cgnr_update(int mode, const CgnrCols& C, const double* L, const doub
 void launch_cgnr_scalar_init(const double* partials3, int nparts, double* scal, int* flags, hipStream_t s);
 void launch_cgnr_scalar_alpha(const double* partials, int nparts, double* scal, int* flags, hipStream_t s);
 void launch_cgnr_scalar_end(const double* partials3, int nparts, double eta, int min_it, int max_it, double* scal, int* flags, hipStream_t s);
+
+// --- the Schur elimination (cgnr_plan.hpp) -----------------------------------------------------------------------------------------
+// E: the e-blocks as column blocks with their slot lists and parts; long_slots[2 l], [2 l + 1]: the range of E.cb_slots of long
+// e-block l.  L: the factors of V_e = bsum_e + D2_e in E.cb_moff's places.  t_e = J_e^T w in plan order, then
+//   kCgnrElimProject: w <- w - J_e V_e^-1 t_e on the rows of e (no two e-blocks share a row);
+//   kCgnrElimBacksub: y_e = V_e^-1 (b_e - t_e), w untouched.
+// partial: [E's num_partials * kCgnrLanes]
+enum { kCgnrElimProject = 0, kCgnrElimBacksub = 1 };
+void launch_cgnr_eliminate(int mode, const CgnrJac& J, const CgnrCols& E, const int* long_slots, const double* L, const double* b, double* w, double* y,
+                           double* partial, const int* flags, hipStream_t s);
+// The pairs (F block g, e-neighbour) of the block diagonal of S and the parts of the pair lists.
+struct CgnrPairs {
+  int num_parts, num_long;
+  const int* part_f; const int* part_begin; const int* part_end; const int* part_out;
+  const int* long_f; const int* long_begin;
+  const int* pair_e;           // per pair: the e-block as a column block of the full list ...
+  const int* cb_size; const int* cb_moff;  // ... whose sizes and matrix offsets these are
+  const int* pair_slot_begin; const int* slot_g; const int* slot_e;
+};
+// sdiag[F.cb_moff[g] + a * size + b] = sum over the pairs (g, e) of (L_e^-1 W_ge^T)^T (L_e^-1 W_ge^T), W_ge summed over the
+// pair's terms first; partial: [P's num_partials * 256]
+void launch_cgnr_schur_diag(const CgnrJac& J, const CgnrCols& F, const CgnrPairs& P, const double* L, double* sdiag, double* partial, hipStream_t s);
 
 // --- the candidate -----------------------------------------------------------------------------------------------------------------
 // x_new = x (+) (y scale) per parameter block; partials[workgroup] of |x - x_new|^2

@@ -10,6 +10,13 @@
 // over the lanes), and a block of more than one part (a LONG block: a camera, a shared calibration block) sums its parts the same
 // way in a second launch: lane l takes parts l, l + kCgnrLanes, ...  Parts and their order are fixed here (jacobian_plan.hpp:
 // cut_parts), so the sum of a block depends on the problem alone, never on a grid size, and no launch uses a floating-point atomic.
+//
+// Schur elimination (sk_options_set_schur_elimination).  E is jacobian_plan.hpp's greedy independent set of the column blocks, F the
+// rest.  The vectors keep the columns of the full tangent space (an e-block's entries are zero while the CG loop runs), so F and
+// E are each a list of column blocks with slot lists and parts of its own (CgnrColumnSubset) that the launches of the products,
+// of the fused update and of the projection are handed in place of the full list.  The block diagonal of S sums, per F block g,
+// over g's distinct e-neighbours in ascending order (a PAIR: every residual block that names both, as (slot of g, slot of e) in
+// row order); the pair lists are cut into parts of kCgnrPartSlots pairs like the slot lists.
 #pragma once
 #include <string>
 #include <vector>
@@ -20,6 +27,14 @@
 namespace sk {
 
 constexpr int kCgnrMaxBlock = 16;   // largest tangent size of a parameter block (the preconditioner's Cholesky lives in one thread)
+
+// Some column blocks of a plan, ascending, as a cols-style list of their own: columns and matrix offsets are the full plan's
+struct CgnrColumnSubset {
+  std::vector<int> cb;                          // the column blocks of cols
+  std::vector<int> cb_col, cb_size, cb_moff;    // per block of the subset: first column, tangent size, first matrix entry
+  std::vector<int> cb_begin, cb_slots;          // [blocks + 1]; slots in row order
+  PartList parts;
+};
 
 struct CgnrPlan {
   EvaluatePlan eval;                   // staging sized for residuals + Jacobian planes
@@ -32,12 +47,21 @@ struct CgnrPlan {
   std::vector<int> cb_moff;             // [column blocks + 1] first entry of the block's size x size matrix (block sums, factors)
   std::vector<int> cb_begin, cb_slots;  // [column blocks + 1]; slots in row order
   PartList parts;                       // of the slot lists cb_slots[cb_begin[c] .. cb_begin[c + 1]), in column-block order
+  // the Schur elimination; all empty without it
+  std::vector<int> cb_elim;             // per column block: 1 in E
+  CgnrColumnSubset F, E;
+  int reduced_cols = 0;                 // tangent size of F
+  std::vector<int> slot_size_f;         // slot_size with 0 on the slots of E: J_F v by the launch of J v
+  std::vector<int> fp_begin;            // [F blocks + 1] the pairs of each F block ...
+  std::vector<int> fp_e;                // ... per pair the e-block (a column block of cols), ascending inside an F block
+  std::vector<int> fp_slot_begin, fp_slot_g, fp_slot_e;  // [pairs + 1]; per term of a pair the slot of g and the slot of e, in row order
+  PartList fp_parts;                    // of the pair lists
 };
 
 // "" when CGNR takes the problem, else why not (SK_ERR_UNSUPPORTED).  Host-callback blocks, a tangent size above kCgnrMaxBlock,
 // DOGLEG, parameter bounds, more than one rank, dense rows.
 std::string cgnr_refusal(const Problem& p, int world, bool dogleg);
 // Returns an sk_status; *why says what is wrong.
-int cgnr_plan_build(const Problem& p, CgnrPlan* plan, std::string* why);
+int cgnr_plan_build(const Problem& p, CgnrPlan* plan, std::string* why, bool schur_elimination = false);
 
 }  // namespace sk

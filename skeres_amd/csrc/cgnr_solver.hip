@@ -9,6 +9,15 @@
 // the flag is set.  The host enqueues cgnr::kBatch iterations, reads the flags back, and stops enqueueing when the loop is done:
 // ordinary stream-ordered launches, no kernel waits for another, no graph.  What is enqueued past the end does nothing, so the
 // step is the same bytes for every batch size.
+//
+// Schur elimination (sk_options_set_schur_elimination; the plan: cgnr_plan.hpp).  With H = J^T J + D^2 = [[U, W], [W^T, V]] over
+// the kept blocks F and an independent set E of eliminated blocks (V block diagonal), the same loop solves S y_F = s with
+// S = U - W V^-1 W^T and s = b_F - W V^-1 b_E, then y_E = V^-1 (b_E - W^T y_F); model cost change, candidate and cost come from
+// the full step as without it.  S is never formed: S v = J_F^T P (J_F v) + D_F^2 v with P = I - J_E V^-1 J_E^T, so an
+// application is the two products over F's index arrays with one projection launch (cgnr_eliminate_kernel) between them.
+// JACOBI is then the block diagonal of S (cgnr_schur_diag_kernel), formed once per linear solve because the radius changes V.
+// The vectors keep the full tangent space's columns; the entries of E stay zero until the back-substitution.  Without the option
+// the launches are the ones above, unchanged.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -41,6 +50,7 @@ class CgnrSolver : public SolverBase {
     s->num_parameter_blocks = (int)problem_->block_size.size();
     s->num_parameters = plan_.cols.num_ambient; s->num_residual_blocks = (int)problem_->rb_functor.size(); s->num_residuals = plan_.eval.num_rows;
     s->preconditioner_type = opt_.preconditioner_type; s->linear_solver_iterations = n_cg_iterations_;
+    s->schur_elimination = schur(); s->eliminated_blocks = (int)plan_.E.cb.size(); s->reduced_columns = plan_.reduced_cols;
   }
   bool stat(const std::string& name, double* value) const override {
     if (name == "cg_iterations") { *value = (double)n_cg_iterations_; return true; }
@@ -49,6 +59,10 @@ class CgnrSolver : public SolverBase {
     if (name == "cg_batches") { *value = (double)n_batches_; return true; }
     if (name == "jacobian_nonzeros") { *value = (double)plan_.eval.num_nonzeros; return true; }
     if (name == "graph_replay") { *value = 0.0; return true; }
+    if (name == "schur_elimination") { *value = schur() ? 1.0 : 0.0; return true; }
+    if (name == "eliminated_blocks") { *value = (double)plan_.E.cb.size(); return true; }
+    if (name == "reduced_columns") { *value = (double)(schur() ? plan_.reduced_cols : n_); return true; }
+    if (name == "schur_diagonal_pairs") { *value = (double)plan_.fp_e.size(); return true; }
     if (name == "tape_blocks") {
       size_t c = 0;
       for (const EvaluateGroup& G : plan_.eval.groups) if (G.functor >= kTapeFunctorBase) c += G.members.size();
@@ -63,6 +77,12 @@ class CgnrSolver : public SolverBase {
   void finish(const double* x_dev, bool jac);
   int enqueue_cg_iteration(int it);
   bool jacobi() const { return opt_.preconditioner_type == SK_JACOBI; }
+  bool schur() const { return opt_.cgnr_schur_elimination; }
+  int setup_schur();
+  int upload_subset(const CgnrColumnSubset& S, DevBuf<int>* bufs, CgnrCols* cols);
+  void project(double* w, const int* flags) {  // w <- w - J_E V^-1 J_E^T w
+    launch_cgnr_eliminate(kCgnrElimProject, jac_, cols_e_, b_e_long_slots_.p, b_L_.p, nullptr, w, nullptr, b_e_part_.p, flags, stream_);
+  }
 
   CgnrPlan plan_;
   int n_ = 0, ng_ = 0, m_ = 0, nb_ = 0, num_pb_ = 0, update_parts_ = 0;
@@ -76,6 +96,17 @@ class CgnrSolver : public SolverBase {
       b_part_, b_jtw_part_, b_bd_part_, b_scal_;
   CgnrJac jac_{};
   CgnrCols cols_{};
+  // the Schur elimination: F's and E's index arrays (kSubsetBufs each), the pairs; s, the sums of S's diagonal and the partial sums.
+  // Without it cg_jac_ and cg_cols_ are jac_ and cols_, and b_rhs_ is b.
+  static constexpr int kSubsetBufs = 10;
+  DevBuf<int> b_f_[kSubsetBufs], b_e_[kSubsetBufs], b_slot_size_f_, b_e_long_slots_, b_fp_part_f_, b_fp_part_begin_, b_fp_part_end_, b_fp_part_out_, b_fp_long_f_,
+      b_fp_long_begin_, b_fp_e_, b_fp_slot_begin_, b_fp_slot_g_, b_fp_slot_e_;
+  DevBuf<double> b_s_, b_sdiag_, b_e_part_, b_sd_part_;
+  CgnrJac cg_jac_{};
+  CgnrCols cg_cols_{}, cols_e_{};
+  CgnrPairs pairs_{};
+  const double* b_rhs_ = nullptr;
+  int cg_update_parts_ = 0;
   double* x_ = nullptr; double* x_new_ = nullptr;
   double* h_scal_ = nullptr;
   int* h_flags_ = nullptr;  // [kCgFlagCount] the CG flags, then the evaluation's failure flag
@@ -91,7 +122,7 @@ int CgnrSolver::setup() {
   }
   if (p.rb_functor.empty()) { set_error("problem has no residual blocks"); return SK_ERR_INVALID_ARGUMENT; }
   std::string why;
-  int rc = cgnr_plan_build(p, &plan_, &why);
+  int rc = cgnr_plan_build(p, &plan_, &why, schur());
   if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
   const EvaluatePlan& E = plan_.eval;
   const TangentColumns& T = plan_.cols;
@@ -148,7 +179,54 @@ int CgnrSolver::setup() {
   cols_.cb_col = b_cb_col_.p; cols_.cb_size = b_cb_size_.p; cols_.cb_moff = b_cb_moff_.p; cols_.cb_slots = b_cb_slots_.p;
   cols_.part_cb = b_part_cb_.p; cols_.part_begin = b_part_begin_.p; cols_.part_end = b_part_end_.p; cols_.part_out = b_part_out_.p;
   cols_.long_cb = b_long_cb_.p; cols_.long_begin = b_long_begin_.p;
+  cg_jac_ = jac_; cg_cols_ = cols_; b_rhs_ = b_b_.p; cg_update_parts_ = update_parts_;
+  if (schur()) { rc = setup_schur(); if (rc != SK_OK) return rc; }
   SK_HIP_TRY(hipStreamSynchronize(s));
+  return SK_OK;
+}
+
+int CgnrSolver::upload_subset(const CgnrColumnSubset& S, DevBuf<int>* b, CgnrCols* cols) {
+  hipStream_t s = stream_;
+  const PartList& L = S.parts;
+  SK_HIP_TRY(upload_padded(b[0], S.cb_col, s)); SK_HIP_TRY(upload_padded(b[1], S.cb_size, s)); SK_HIP_TRY(upload_padded(b[2], S.cb_moff, s));
+  SK_HIP_TRY(upload_padded(b[3], S.cb_slots, s));
+  SK_HIP_TRY(upload_padded(b[4], L.owner, s)); SK_HIP_TRY(upload_padded(b[5], L.begin, s)); SK_HIP_TRY(upload_padded(b[6], L.end, s)); SK_HIP_TRY(upload_padded(b[7], L.out, s));
+  SK_HIP_TRY(upload_padded(b[8], L.long_owner, s)); SK_HIP_TRY(b[9].upload(L.long_begin, s));
+  cols->num_cb = (int)S.cb.size(); cols->num_parts = (int)L.owner.size(); cols->num_long = (int)L.long_owner.size();
+  cols->cb_col = b[0].p; cols->cb_size = b[1].p; cols->cb_moff = b[2].p; cols->cb_slots = b[3].p;
+  cols->part_cb = b[4].p; cols->part_begin = b[5].p; cols->part_end = b[6].p; cols->part_out = b[7].p;
+  cols->long_cb = b[8].p; cols->long_begin = b[9].p;
+  return SK_OK;
+}
+
+// The index arrays of F, E and the pairs; the loop then runs on F's (cg_jac_, cg_cols_) with s as its right-hand side.
+int CgnrSolver::setup_schur() {
+  hipStream_t s = stream_;
+  int rc = upload_subset(plan_.F, b_f_, &cg_cols_);
+  if (rc == SK_OK) rc = upload_subset(plan_.E, b_e_, &cols_e_);
+  if (rc != SK_OK) return rc;
+  SK_HIP_TRY(upload_padded(b_slot_size_f_, plan_.slot_size_f, s));
+  cg_jac_.slot_size = b_slot_size_f_.p;
+  std::vector<int> long_slots;
+  for (int e : plan_.E.parts.long_owner) { long_slots.push_back(plan_.E.cb_begin[e]); long_slots.push_back(plan_.E.cb_begin[e + 1]); }
+  SK_HIP_TRY(upload_padded(b_e_long_slots_, long_slots, s));
+  const PartList& L = plan_.fp_parts;
+  SK_HIP_TRY(upload_padded(b_fp_part_f_, L.owner, s)); SK_HIP_TRY(upload_padded(b_fp_part_begin_, L.begin, s)); SK_HIP_TRY(upload_padded(b_fp_part_end_, L.end, s));
+  SK_HIP_TRY(upload_padded(b_fp_part_out_, L.out, s)); SK_HIP_TRY(upload_padded(b_fp_long_f_, L.long_owner, s)); SK_HIP_TRY(b_fp_long_begin_.upload(L.long_begin, s));
+  SK_HIP_TRY(upload_padded(b_fp_e_, plan_.fp_e, s)); SK_HIP_TRY(b_fp_slot_begin_.upload(plan_.fp_slot_begin, s));
+  SK_HIP_TRY(upload_padded(b_fp_slot_g_, plan_.fp_slot_g, s)); SK_HIP_TRY(upload_padded(b_fp_slot_e_, plan_.fp_slot_e, s));
+  pairs_.num_parts = (int)L.owner.size(); pairs_.num_long = (int)L.long_owner.size();
+  pairs_.part_f = b_fp_part_f_.p; pairs_.part_begin = b_fp_part_begin_.p; pairs_.part_end = b_fp_part_end_.p; pairs_.part_out = b_fp_part_out_.p;
+  pairs_.long_f = b_fp_long_f_.p; pairs_.long_begin = b_fp_long_begin_.p;
+  pairs_.pair_e = b_fp_e_.p; pairs_.cb_size = b_cb_size_.p; pairs_.cb_moff = b_cb_moff_.p;
+  pairs_.pair_slot_begin = b_fp_slot_begin_.p; pairs_.slot_g = b_fp_slot_g_.p; pairs_.slot_e = b_fp_slot_e_.p;
+  SK_HIP_TRY(b_s_.alloc((size_t)n_)); SK_HIP_TRY(b_s_.zero(s));
+  SK_HIP_TRY(b_q_.zero(s));  // (the entries of E are never written and are read by the dot product p . q)
+  SK_HIP_TRY(b_sdiag_.alloc((size_t)plan_.cb_moff.back()));
+  SK_HIP_TRY(b_e_part_.alloc(std::max<size_t>((size_t)plan_.E.parts.num_partials * kCgnrLanes, 1)));
+  SK_HIP_TRY(b_sd_part_.alloc(std::max<size_t>((size_t)L.num_partials * 256, 1)));
+  b_rhs_ = b_s_.p;
+  cg_update_parts_ = ((int)plan_.F.cb.size() + kCgnrBlockChunk - 1) / kCgnrBlockChunk;
   return SK_OK;
 }
 
@@ -197,19 +275,21 @@ int CgnrSolver::enqueue_cg_iteration(int it) {
   hipStream_t s = stream_;
   const int* flags = b_flags_.p;
   const double* L = jacobi() ? b_L_.p : nullptr;
-  launch_cgnr_jp(jac_, b_z_.p, b_p_.p, b_scal_.p, b_w_.p, flags, s);                                                      // w = J p, p = z + beta p
-  launch_cgnr_jtw(kCgnrJtwCg, jac_, cols_, b_w_.p, b_D2_.p, b_z_.p, b_p_.p, b_scal_.p, b_q_.p, b_jtw_part_.p, flags, s);   // q = J^T w + D2 p; p stored
+  launch_cgnr_jp(cg_jac_, b_z_.p, b_p_.p, b_scal_.p, b_w_.p, flags, s);                                                      // w = J p, p = z + beta p
+  if (schur()) project(b_w_.p, flags);
+  launch_cgnr_jtw(kCgnrJtwCg, cg_jac_, cg_cols_, b_w_.p, b_D2_.p, b_z_.p, b_p_.p, b_scal_.p, b_q_.p, b_jtw_part_.p, flags, s);   // q = J^T w + D2 p; p stored
   launch_cgnr_dot(0, b_p_.p, b_q_.p, n_, b_part_.p, flags, s);
   launch_cgnr_scalar_alpha(b_part_.p, (n_ + kCgnrDotChunk - 1) / kCgnrDotChunk, b_scal_.p, b_flags_.p, s);                // alpha = rho / p . q
   if (it % cgnr::kResidualResetPeriod == 0) {  // res = b - A x
     launch_cgnr_axpy(b_scal_.p, b_p_.p, b_y_.p, n_, flags, s);
-    launch_cgnr_jp(jac_, b_y_.p, nullptr, nullptr, b_w_.p, flags, s);
-    launch_cgnr_jtw(kCgnrJtwVector, jac_, cols_, b_w_.p, b_D2_.p, b_y_.p, nullptr, nullptr, b_q_.p, b_jtw_part_.p, flags, s);
-    launch_cgnr_update(kCgnrReset, cols_, L, b_b_.p, b_p_.p, b_q_.p, b_scal_.p, b_y_.p, b_res_.p, b_z_.p, b_part_.p, flags, s);
+    launch_cgnr_jp(cg_jac_, b_y_.p, nullptr, nullptr, b_w_.p, flags, s);
+    if (schur()) project(b_w_.p, flags);
+    launch_cgnr_jtw(kCgnrJtwVector, cg_jac_, cg_cols_, b_w_.p, b_D2_.p, b_y_.p, nullptr, nullptr, b_q_.p, b_jtw_part_.p, flags, s);
+    launch_cgnr_update(kCgnrReset, cg_cols_, L, b_rhs_, b_p_.p, b_q_.p, b_scal_.p, b_y_.p, b_res_.p, b_z_.p, b_part_.p, flags, s);
   } else {     // x += alpha p, res -= alpha q
-    launch_cgnr_update(kCgnrStep, cols_, L, b_b_.p, b_p_.p, b_q_.p, b_scal_.p, b_y_.p, b_res_.p, b_z_.p, b_part_.p, flags, s);
+    launch_cgnr_update(kCgnrStep, cg_cols_, L, b_rhs_, b_p_.p, b_q_.p, b_scal_.p, b_y_.p, b_res_.p, b_z_.p, b_part_.p, flags, s);
   }
-  launch_cgnr_scalar_end(b_part_.p, update_parts_, opt_.eta, opt_.min_linear_solver_iterations, opt_.max_linear_solver_iterations, b_scal_.p, b_flags_.p, s);
+  launch_cgnr_scalar_end(b_part_.p, cg_update_parts_, opt_.eta, opt_.min_linear_solver_iterations, opt_.max_linear_solver_iterations, b_scal_.p, b_flags_.p, s);
   return SK_OK;
 }
 
@@ -221,16 +301,31 @@ int CgnrSolver::linear_solve(double radius, LinearSolve* out) {
   const int batch = dev_knobs().cgnr_batch > 0 ? dev_knobs().cgnr_batch : cgnr::kBatch;
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   SK_HIP_TRY(hipMemsetAsync(b_flags_.p, 0, kCgFlagCount * sizeof(int), s));
-  launch_cgnr_precond_factor(cols_, b_bsum_.p, opt_.min_lm_diagonal, opt_.max_lm_diagonal, radius, b_D2_.p, jacobi() ? b_L_.p : nullptr, b_flags_.p, s);
+  launch_cgnr_precond_factor(cols_, b_bsum_.p, opt_.min_lm_diagonal, opt_.max_lm_diagonal, radius, b_D2_.p, jacobi() || schur() ? b_L_.p : nullptr, b_flags_.p, s);
+  if (schur()) {  // V's factors are in place: the block diagonal of S over F's (JACOBI), s = -J_F^T P r
+    if (jacobi()) {
+      launch_cgnr_schur_diag(jac_, cg_cols_, pairs_, b_L_.p, b_sdiag_.p, b_sd_part_.p, s);
+      launch_cgnr_precond_factor(cg_cols_, b_bsum_.p, opt_.min_lm_diagonal, opt_.max_lm_diagonal, radius, b_D2_.p, b_L_.p, b_flags_.p, s, b_sdiag_.p);
+    }
+    SK_HIP_TRY(hipMemcpyAsync(b_w_.p, b_r_.p, (size_t)m_ * sizeof(double), hipMemcpyDeviceToDevice, s));
+    project(b_w_.p, nullptr);
+    launch_cgnr_jtw(kCgnrJtwNegated, jac_, cg_cols_, b_w_.p, nullptr, nullptr, nullptr, nullptr, b_s_.p, b_jtw_part_.p, nullptr, s);
+  }
   SK_HIP_TRY(hipEventRecord(ev_[kEvAssemble], s));
 
   // x = 0, res = b, z = M^-1 res, rho; then iterations in batches until the device says done
   SK_HIP_TRY(hipMemsetAsync(b_y_.p, 0, (size_t)n_ * sizeof(double), s));
   SK_HIP_TRY(hipMemsetAsync(b_p_.p, 0, (size_t)n_ * sizeof(double), s));
-  launch_cgnr_update(kCgnrInit, cols_, jacobi() ? b_L_.p : nullptr, b_b_.p, b_p_.p, b_q_.p, b_scal_.p, b_y_.p, b_res_.p, b_z_.p, b_part_.p, nullptr, s);
-  launch_cgnr_scalar_init(b_part_.p, update_parts_, b_scal_.p, b_flags_.p, s);
+  launch_cgnr_update(kCgnrInit, cg_cols_, jacobi() ? b_L_.p : nullptr, b_rhs_, b_p_.p, b_q_.p, b_scal_.p, b_y_.p, b_res_.p, b_z_.p, b_part_.p, nullptr, s);
+  launch_cgnr_scalar_init(b_part_.p, cg_update_parts_, b_scal_.p, b_flags_.p, s);
   int enqueued = 0;
-  for (;;) {
+  const bool no_loop = schur() && plan_.F.cb.empty();  // every moving block is independent of the others: the back-substitution is the solve
+  if (no_loop) {
+    SK_HIP_TRY(hipMemcpyAsync(h_flags_, b_flags_.p, kCgFlagCount * sizeof(int), hipMemcpyDeviceToHost, s));
+    SK_HIP_TRY(hipStreamSynchronize(s));
+    h_flags_[kCgIt] = 0; h_flags_[kCgDone] = 1; h_flags_[kCgStatus] = cgnr::kConverged;
+  }
+  while (!no_loop) {
     for (int k = 0; k < batch && enqueued < max_it; ++k) { int rc = enqueue_cg_iteration(++enqueued); if (rc) return rc; }
     SK_HIP_TRY(hipMemcpyAsync(h_flags_, b_flags_.p, kCgFlagCount * sizeof(int), hipMemcpyDeviceToHost, s));
     SK_HIP_TRY(hipStreamSynchronize(s));
@@ -249,6 +344,10 @@ int CgnrSolver::linear_solve(double radius, LinearSolve* out) {
     return SK_OK;
   }
 
+  if (schur()) {  // y_E = V^-1 (b_E - J_E^T (J_F y_F))
+    launch_cgnr_jp(cg_jac_, b_y_.p, nullptr, nullptr, b_w_.p, nullptr, s);
+    launch_cgnr_eliminate(kCgnrElimBacksub, jac_, cols_e_, b_e_long_slots_.p, b_L_.p, b_b_.p, b_w_.p, b_y_.p, b_e_part_.p, nullptr, s);
+  }
   // the model's change from the step itself, the candidate through Plus, its cost
   launch_cgnr_jp(jac_, b_y_.p, nullptr, nullptr, b_w_.p, nullptr, s);
   launch_cgnr_dot(1, b_w_.p, b_r_.p, m_, b_part_.p, nullptr, s);

@@ -85,6 +85,7 @@ struct Options {  // Solver.Options; Ceres 1.x defaults
   int preconditioner_type = SK_JACOBI;
   double eta = 0.1;
   int max_linear_solver_iterations = 500, min_linear_solver_iterations = 0;
+  bool cgnr_schur_elimination = false;  // sk_options_set_schur_elimination: CG on the implicit Schur complement of an independent set (cgnr_plan.hpp)
   int device = -1;
   hipStream_t stream = nullptr;
   bool stream_set = false;
@@ -173,6 +174,8 @@ struct Summary {
   int trust_region_strategy_type = SK_LEVENBERG_MARQUARDT;
   int preconditioner_type = SK_JACOBI;  // CGNR
   long linear_solver_iterations = 0;    // CGNR: total over the solve
+  bool schur_elimination = false;       // CGNR with sk_options_set_schur_elimination: the eliminated blocks and the columns CG runs on
+  int eliminated_blocks = 0, reduced_columns = 0;
   std::string device_name;
   std::string brief, full;
   void build_reports();

@@ -42,15 +42,7 @@ int schur_plan_build(CovariancePlan& C, std::string* why) {
   for (int c = 0; c < ncb; ++c) nb_begin[c + 1] = nb_begin[c] + deg[c];
   std::vector<int> nb(nb_begin[ncb]), fill(nb_begin.begin(), nb_begin.end() - 1);
   for (int q = 0; q < npairs; ++q) if (C.pair_i[q] != C.pair_j[q]) { nb[fill[C.pair_i[q]]++] = C.pair_j[q]; nb[fill[C.pair_j[q]]++] = C.pair_i[q]; }
-  std::vector<int> order(ncb);
-  for (int c = 0; c < ncb; ++c) order[c] = c;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return deg[a] < deg[b]; });  // (column blocks ascend with the parameter-block index)
-  C.cb_elim.assign(ncb, 0);
-  for (int c : order) {
-    bool free = true;
-    for (int k = nb_begin[c]; k < nb_begin[c + 1] && free; ++k) free = !C.cb_elim[nb[k]];
-    C.cb_elim[c] = free ? 1 : 0;
-  }
+  greedy_independent_set(nb_begin, nb, &C.cb_elim);  // (column blocks ascend with the parameter-block index)
   C.cb_red.assign(ncb, 0);
   long long red = 0;
   for (int c = 0; c < ncb; ++c) {

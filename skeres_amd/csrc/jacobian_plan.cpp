@@ -50,6 +50,19 @@ void cut_parts(const std::vector<int>& begin_of, PartList* parts) {
   }
 }
 
+void greedy_independent_set(const std::vector<int>& nb_begin, const std::vector<int>& nb, std::vector<int>* in_set) {
+  const int ncb = (int)nb_begin.size() - 1;
+  std::vector<int> order(ncb);
+  for (int c = 0; c < ncb; ++c) order[c] = c;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return nb_begin[a + 1] - nb_begin[a] < nb_begin[b + 1] - nb_begin[b]; });
+  in_set->assign(ncb, 0);
+  for (int c : order) {
+    bool free = true;
+    for (int k = nb_begin[c]; k < nb_begin[c + 1] && free; ++k) free = !(*in_set)[nb[k]];
+    (*in_set)[c] = free ? 1 : 0;
+  }
+}
+
 std::string block_size_refusal(const Problem& p, const char* feature, int limit, bool constants_too) {
   char buf[256];
   for (size_t b = 0; b < p.block_size.size(); ++b) {

@@ -1,5 +1,6 @@
 // What the users of Problem::Evaluate's block-sparse Jacobian share on the host (cgnr_plan.hpp, covariance_plan.hpp): the tangent
-// columns of the parameter blocks that move, the cutting of a summation list into parts, and the refusal of blocks that are too
+// columns of the parameter blocks that move, the cutting of a summation list into parts, the independent set that a Schur
+// elimination removes, and the refusal of blocks that are too
 // large for one lane — plain C++ over a Problem and an EvaluatePlan, compiled without the device headers like evaluate_plan.cpp.
 #pragma once
 #include <string>
@@ -41,6 +42,12 @@ struct PartList {
   int num_partials = 0;
 };
 void cut_parts(const std::vector<int>& begin_of, PartList* parts);
+
+// The independent set of a Schur elimination (covariance_plan.hpp, cgnr_plan.hpp).  Two column blocks are neighbours when a residual
+// block names both; nb[nb_begin[c] .. nb_begin[c + 1]) are the DISTINCT neighbours of column block c.  The blocks are visited in
+// ascending order of (number of distinct neighbours, column block), which ascends with the parameter-block index, and a block
+// joins the set when none of its neighbours is in it.  in_set: per column block 1 or 0.
+void greedy_independent_set(const std::vector<int>& nb_begin, const std::vector<int>& nb, std::vector<int>* in_set);
 
 // "" when every parameter block fits one lane, else why not, in `feature`'s name ("CGNR", "Covariance"): a parameterized block of
 // size above `limit`, or a tangent size above it.  constants_too: constant blocks are held to the limit as well.

@@ -437,6 +437,10 @@ void Summary::build_reports() {
   if (linear_solver_type == SK_CGNR) {
     snprintf(b, sizeof(b), "Preconditioner         %22s\nLinear solver iterations    % 12ld\n", preconditioner_type == SK_JACOBI ? "JACOBI" : "IDENTITY", linear_solver_iterations);
     f += b;
+    if (schur_elimination) {
+      snprintf(b, sizeof(b), "Schur elimination      implicit: %d blocks eliminated, %d reduced columns\n", eliminated_blocks, reduced_columns);
+      f += b;
+    }
   }
   if (linear_solver_type == SK_DENSE_SCHUR) {
     snprintf(b, sizeof(b), "Schur structure                        2,3,9\nE blocks (eliminated)       % 12d\nF blocks                    % 12d\n", num_e_blocks, num_f_blocks);
