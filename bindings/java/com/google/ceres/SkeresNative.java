@@ -145,6 +145,17 @@ public final class SkeresNative {
   public static native int skOptionsSetMaxLinearSolverIterations(long o, int v);
   public static native int skOptionsSetMinLinearSolverIterations(long o, int v);
   public static native int skOptionsSetSchurElimination(long o, int v);
+  // inner iterations (Solver::Options::use_inner_iterations, inner_iteration_tolerance, inner_iteration_ordering): CGNR
+  public static native int skOptionsSetUseInnerIterations(long o, int v);
+  public static native int skOptionsSetInnerIterationTolerance(long o, double v);
+  public static native int skOptionsGetUseInnerIterations(long o);
+  public static native double skOptionsGetInnerIterationTolerance(long o);
+  // blocks: native pointers of the parameter blocks; groups: a group id each; both empty: automatic
+  public static native int skOptionsSetInnerIterationOrdering(long o, long[] blocks, int[] groups);
+  // o: options or 0 (automatic); groupOfBlock: [parameter blocks] or null (-1: not refined); counts: {groups}
+  public static native int skInnerIterationPlan(long p, long o, int[] groupOfBlock, int[] counts);
+  // iterations, status: [parameter blocks] of the last refinement (-1: not refined)
+  public static native int skSolverInnerIterationBlocks(long s, int[] iterations, int[] status);
   public static native int skOptionsSetCholeskyEnvelope(long o, int v);
   public static native int skOptionsSetCholeskyDissection(long o, int v);
   public static native int skOptionsSetCholeskyBorder(long o, int v);

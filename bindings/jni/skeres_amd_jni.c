@@ -319,6 +319,53 @@ SK_OPT_DBL(skOptionsSetEta, sk_options_set_eta)
 SK_OPT_INT(skOptionsSetMaxLinearSolverIterations, sk_options_set_max_linear_solver_iterations)
 SK_OPT_INT(skOptionsSetMinLinearSolverIterations, sk_options_set_min_linear_solver_iterations)
 SK_OPT_INT(skOptionsSetSchurElimination, sk_options_set_schur_elimination)
+SK_OPT_INT(skOptionsSetUseInnerIterations, sk_options_set_use_inner_iterations)
+SK_OPT_DBL(skOptionsSetInnerIterationTolerance, sk_options_set_inner_iteration_tolerance)
+SK_JNI(jint, skOptionsGetUseInnerIterations)(JNIEnv* env, jclass c, jlong o) { (void)env; (void)c; return sk_options_get_use_inner_iterations(PTR(sk_options, o)); }
+SK_JNI(jdouble, skOptionsGetInnerIterationTolerance)(JNIEnv* env, jclass c, jlong o) { (void)env; (void)c; return sk_options_get_inner_iteration_tolerance(PTR(sk_options, o)); }
+/* blocks: native pointers of the parameter blocks (DoubleArray.cast); groups: a group id each; both empty: automatic */
+SK_JNI(jint, skOptionsSetInnerIterationOrdering)(JNIEnv* env, jclass c, jlong o, jlongArray blocks, jintArray groups) {
+  (void)c;
+  const jsize n = (*env)->GetArrayLength(env, blocks);
+  if ((*env)->GetArrayLength(env, groups) != n) return check(env, SK_ERR_INVALID_ARGUMENT);
+  jlong* b = (*env)->GetLongArrayElements(env, blocks, NULL);
+  jint* g = (*env)->GetIntArrayElements(env, groups, NULL);
+  double** ptrs = (double**)malloc(sizeof(double*) * (size_t)(n > 0 ? n : 1));
+  int* ids = (int*)malloc(sizeof(int) * (size_t)(n > 0 ? n : 1));
+  int rc = SK_ERR_INVALID_ARGUMENT;
+  if (ptrs && ids) {
+    for (jsize i = 0; i < n; ++i) { ptrs[i] = PTR(double, b[i]); ids[i] = (int)g[i]; }
+    rc = sk_options_set_inner_iteration_ordering(PTR(sk_options, o), ptrs, ids, (int)n);
+  }
+  free(ptrs); free(ids);
+  (*env)->ReleaseLongArrayElements(env, blocks, b, 0);
+  (*env)->ReleaseIntArrayElements(env, groups, g, 0);
+  return check(env, rc);
+}
+/* o: options or 0 (automatic); groupOfBlock: [parameter blocks] or null; counts: {groups} */
+SK_JNI(jint, skInnerIterationPlan)(JNIEnv* env, jclass c, jlong p, jlong o, jintArray groupOfBlock, jintArray counts) {
+  (void)c;
+  int n = 0;
+  jint* of = groupOfBlock ? (*env)->GetIntArrayElements(env, groupOfBlock, NULL) : NULL;
+  const int rc = sk_inner_iteration_plan(PTR(sk_problem, p), PTR(sk_options, o), (int*)of, &n);
+  if (of) (*env)->ReleaseIntArrayElements(env, groupOfBlock, of, 0);
+  if (rc == SK_OK) {
+    jint* k = (*env)->GetIntArrayElements(env, counts, NULL);
+    k[0] = n;
+    (*env)->ReleaseIntArrayElements(env, counts, k, 0);
+  }
+  return check(env, rc);
+}
+/* iterations, status: [parameter blocks] */
+SK_JNI(jint, skSolverInnerIterationBlocks)(JNIEnv* env, jclass c, jlong s, jintArray iterations, jintArray status) {
+  (void)c;
+  jint* it = (*env)->GetIntArrayElements(env, iterations, NULL);
+  jint* st = (*env)->GetIntArrayElements(env, status, NULL);
+  const int rc = sk_solver_inner_iteration_blocks(PTR(sk_solver, s), (int*)it, (int*)st);
+  (*env)->ReleaseIntArrayElements(env, iterations, it, 0);
+  (*env)->ReleaseIntArrayElements(env, status, st, 0);
+  return check(env, rc);
+}
 SK_OPT_INT(skOptionsSetCholeskyEnvelope, sk_options_set_cholesky_envelope)
 SK_OPT_INT(skOptionsSetCholeskyDissection, sk_options_set_cholesky_dissection)
 SK_OPT_INT(skOptionsSetCholeskyBorder, sk_options_set_cholesky_border)

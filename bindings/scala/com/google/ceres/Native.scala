@@ -285,6 +285,17 @@ object Solver {
     def setDistributionMode(mode: Int): Unit = SkeresNative.skOptionsSetDistributionMode(handle, mode)
     /** CGNR: conjugate gradients on the implicit Schur complement of an independent set of parameter blocks (default off) */
     def setSchurElimination(on: Boolean): Unit = SkeresNative.skOptionsSetSchurElimination(handle, if (on) 1 else 0)
+    /** CGNR: after every trust-region step each parameter block of an independent set is minimised on its own, set after set
+      * (Solver::Options::use_inner_iterations; default off; every other linear solver type refuses it when the solver is created) */
+    def setUseInnerIterations(on: Boolean): Unit = SkeresNative.skOptionsSetUseInnerIterations(handle, if (on) 1 else 0)
+    def getUseInnerIterations: Boolean = SkeresNative.skOptionsGetUseInnerIterations(handle) != 0
+    def setInnerIterationTolerance(v: Double): Unit = SkeresNative.skOptionsSetInnerIterationTolerance(handle, v)
+    def getInnerIterationTolerance: Double = SkeresNative.skOptionsGetInnerIterationTolerance(handle)
+    /** group id -> the native pointers of its parameter blocks (ceres::ParameterBlockOrdering's group_to_elements); empty: automatic */
+    def setInnerIterationOrdering(groupToElements: Map[Int, Seq[Long]]): Unit = {
+      val pairs = groupToElements.toSeq.sortBy(_._1).flatMap { case (g, blocks) => blocks.map(b => (b, g)) }
+      SkeresNative.skOptionsSetInnerIterationOrdering(handle, pairs.map(_._1).toArray, pairs.map(_._2).toArray)
+    }
     /** this JVM is rank `rank` of `world`, one per GPU; the collective is the library's own RCCL all-reduce */
     def setDistributedRccl(rank: Int, world: Int, uniqueId: Array[Byte]): Unit = {
       rccl = SkeresNative.skAllreduceRcclInit(rank, world, uniqueId)

@@ -56,6 +56,10 @@ void initGoogleLogging(const char* name) { sk_init_logging(name); }
 // (sk_covariance_options_* and sk_covariance_* too: ceres::Covariance and ceres::Covariance::Options, which the reference's ceres.i #include's and
 // %include's with ceres/covariance.h, ceres.i:29,141; Covariance in Native.scala binds them by hand over Java arrays;
 // sk_covariance_options_set_schur_elimination, sk_covariance_elimination_plan and sk_problem_parameter_block_index have no reference counterpart)
+// (sk_options_set_use_inner_iterations, _inner_iteration_tolerance and _inner_iteration_ordering with the two getters too:
+// Solver::Options::use_inner_iterations, inner_iteration_tolerance and inner_iteration_ordering, which the reference's ceres.i
+// %include's with ceres/solver.h and ceres/ordered_groups.h, ceres.i:149-151; Solver.Options in Native.scala binds them by hand;
+// sk_inner_iteration_plan and sk_solver_inner_iteration_blocks have no reference counterpart)
 %include "skeres_amd.h"
 
 // load the native libraries as the reference's module class does (ceres.i:213-223)

@@ -504,6 +504,31 @@ int sk_options_set_schur_elimination(sk_options* o, int on);
  * of F, the e-blocks on more than 64 residual blocks (summed in two launches) and the (F block, e-block) pairs.  Any pointer may be
  * NULL.  SK_ERR_UNSUPPORTED as a CGNR solver on one rank with LEVENBERG_MARQUARDT refuses the problem. */
 int sk_cgnr_elimination_plan(const sk_problem* p, int* eliminated_of_block, int* num_eliminated, int* reduced_columns, int* long_eliminated_blocks, int* fe_pairs);
+/* Inner iterations (Solver::Options::use_inner_iterations, inner_iteration_tolerance, inner_iteration_ordering; Ceres 1.x,
+ * restated from memory).  Default off; under SK_CGNR only, with or without sk_options_set_schur_elimination: every other linear
+ * solver type makes sk_solver_create return SK_ERR_UNSUPPORTED with a message that names the solver.  After every trust-region
+ * step that is valid and has a positive model cost change, each parameter block of an independent set (group 0) is minimised on
+ * its own, all the others held, then group 1 follows, and so on.  One such solve is the Levenberg-Marquardt loop of this library
+ * with Ceres' default options (50 iterations, function tolerance 1e-6, gradient tolerance 1e-10, parameter tolerance 1e-8,
+ * initial radius 1e4), not the outer solve's; its linear solve is a Cholesky factorisation of the block's damped normal matrix
+ * (Ceres: DENSE_QR).  With c the current cost, c_tr the candidate's and c_in the refined candidate's: model_cost_change += c_tr -
+ * c_in; the step is successful when rho > min_relative_decrease or c_in < c; the refinement switches itself off for the rest of
+ * the solve once 1 - c_in / c_tr <= inner_iteration_tolerance (default 1e-3; >= 0).
+ * Ordering: n = 0 (the default) is automatic — group 0 the greedy independent set of sk_options_set_schur_elimination on the moving
+ * blocks, group k the same rule on the blocks still ungrouped with their neighbours counted among those alone (bundle adjustment:
+ * the points, then the cameras).  n > 0: blocks[i] is refined in group groups[i] (ascending ids; >= 0); unlisted blocks are not
+ * refined and constant blocks are ignored.  The pointers are copied, not the memory.  sk_solver_create returns
+ * SK_ERR_INVALID_ARGUMENT for a pointer that is no parameter block of the problem and for a group that is not an independent
+ * set (the message names the two blocks that a residual block joins). */
+int sk_options_set_use_inner_iterations(sk_options* o, int on);
+int sk_options_get_use_inner_iterations(const sk_options* o);
+int sk_options_set_inner_iteration_tolerance(sk_options* o, double v);
+double sk_options_get_inner_iteration_tolerance(const sk_options* o);
+int sk_options_set_inner_iteration_ordering(sk_options* o, double* const* blocks, const int* groups, int n);
+/* (no reference counterpart) the groups of the options' ordering (o == NULL: automatic) for this problem, from host data alone
+ * (no device): group_of_block [parameter blocks]: the group, -1 not refined; the number of groups.  Any output may be NULL.
+ * SK_ERR_UNSUPPORTED as a CGNR solver refuses the problem, SK_ERR_INVALID_ARGUMENT as sk_solver_create refuses the ordering. */
+int sk_inner_iteration_plan(const sk_problem* p, const sk_options* o, int* group_of_block, int* num_groups);
 /* MI355X-side knobs (no reference counterpart) */
 int sk_options_set_device(sk_options* o, int hip_device);             /* default: current device */
 int sk_options_set_stream(sk_options* o, void* hip_stream);           /* default: a private stream */
@@ -656,7 +681,8 @@ const char* sk_summary_full_report(const sk_summary* s);     /* Summary.fullRepo
  * 5 trust_region_radius, 6 step_is_valid, 7 step_is_successful,
  * 8 step_size (the line search's alpha under parameter bounds; 1 without), 9 line_search_evaluations (candidate costs
  * evaluated in the iteration: the ls_iter column; 1 without bounds), 10 linear_solver_iterations (CGNR: the CG iterations of
- * the iteration's linear solve; 0 for the factorisation solvers) */
+ * the iteration's linear solve; 0 for the factorisation solvers), 11 inner_iteration_rounds (use_inner_iterations: the
+ * lock-step rounds that refined the iteration's candidate; 0 when it was not refined) */
 int sk_summary_num_logged_iterations(const sk_summary* s);
 double sk_summary_iteration_field(const sk_summary* s, int iteration, int field);
 /* Device time per phase, seconds, summed over the solve (HIP events on the
@@ -738,10 +764,17 @@ int sk_solver_distribution(const sk_solver* s, double* allreduce_seconds, double
  *   the first), "cg_batches" reads of the done flag, "jacobian_nonzeros" stored entries of the block-sparse Jacobian,
  *   "schur_elimination" (0 or 1), "eliminated_blocks", "reduced_columns" (all columns without the elimination),
  *   "schur_diagonal_pairs": sk_options_set_schur_elimination
+ *   "inner_iteration_steps" LM iterations whose candidate was refined, "inner_iteration_rounds" lock-step rounds since the solver
+ *   was created, "inner_iterations_enabled" (1 while the refinement is on), "inner_iteration_seconds" wall time spent refining,
+ *   "inner_iteration_groups": sk_options_set_use_inner_iterations
  * dense rows (DENSE_NORMAL_CHOLESKY over one parameter block):
  *   "jtj_flops_algorithmic" m n (n + 1): SURVEY.md section 8(d)'s figure for J^T J (sk_solver_syrk_flops_per_solve counts
  *                           the padded 128 x 128 tiles the launch computes) */
 int sk_solver_stat(const sk_solver* s, const char* name, double* value);
+/* (no reference counterpart) use_inner_iterations: per parameter block the Levenberg-Marquardt iterations of its solve in the last
+ * refinement and how it ended (1 gradient tolerance, 2 parameter tolerance, 3 function tolerance, 4 iteration limit, 5 consecutive
+ * invalid steps, 6 minimum radius); -1 for a block that is not refined, and before the first refinement.  Either output may be NULL. */
+int sk_solver_inner_iteration_blocks(sk_solver* s, int* iterations, int* status);
 
 /* ---- multi-GPU sharding (host logic, no device needed) -----------------------
  * How sk_solve splits a bundle-adjustment-shaped problem over `world` ranks

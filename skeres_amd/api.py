@@ -123,6 +123,13 @@ _SIGS = {
     "sk_options_set_cholesky_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "sk_options_set_schur_elimination": (C.c_int, [C.c_void_p, C.c_int]),
     "sk_cgnr_elimination_plan": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _ip, _ip]),
+    "sk_options_set_use_inner_iterations": (C.c_int, [C.c_void_p, C.c_int]),
+    "sk_options_get_use_inner_iterations": (C.c_int, [C.c_void_p]),
+    "sk_options_set_inner_iteration_tolerance": (C.c_int, [C.c_void_p, C.c_double]),
+    "sk_options_get_inner_iteration_tolerance": (C.c_double, [C.c_void_p]),
+    "sk_options_set_inner_iteration_ordering": (C.c_int, [C.c_void_p, C.POINTER(_dp), _ip, C.c_int]),
+    "sk_inner_iteration_plan": (C.c_int, [C.c_void_p, C.c_void_p, _ip, _ip]),
+    "sk_solver_inner_iteration_blocks": (C.c_int, [C.c_void_p, _ip, _ip]),
     "sk_options_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sk_options_set_distributed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ALLREDUCE_FN, C.c_void_p]),
     "sk_options_set_reduce_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -1423,6 +1430,17 @@ class Solver:
         return dict(eliminated_of_block=of_block[:nb].copy(), num_eliminated=n.value, reduced_columns=cols.value,
                     long_eliminated_blocks=long_e.value, fe_pairs=pairs.value)
 
+    @staticmethod
+    def innerIterationPlan(problem, options=None):
+        """The groups of Options.setUseInnerIterations for this problem and these options' ordering (None: automatic), from host
+        data alone (sk_inner_iteration_plan): a dict with group_of_block (per parameter block: its group, -1 not refined) and
+        num_groups."""
+        nb = lib().sk_problem_num_parameter_blocks(problem._h)
+        of_block = np.zeros(max(nb, 1), dtype=np.int32)
+        n = C.c_int()
+        _check_arg(lib().sk_inner_iteration_plan(problem._h, options._h if options is not None else None, of_block.ctypes.data_as(_ip), C.byref(n)))
+        return dict(group_of_block=of_block[:nb].copy(), num_groups=n.value)
+
     class Options:
         def __init__(self):
             self._h = lib().sk_options_new()
@@ -1469,6 +1487,29 @@ class Solver:
             """CGNR: conjugate gradients on the implicit Schur complement of an independent set of parameter blocks (default off;
             no effect under the other solver types).  JACOBI is then the block diagonal of the Schur complement."""
             _check(lib().sk_options_set_schur_elimination(self._h, int(bool(on))))
+
+        def setUseInnerIterations(self, on):
+            """CGNR: after every trust-region step each parameter block of an independent set is minimised on its own, set after
+            set (Ceres' use_inner_iterations; default off).  Every other linear solver type refuses it when the solver is created."""
+            _check(lib().sk_options_set_use_inner_iterations(self._h, int(bool(on))))
+
+        def useInnerIterations(self): return bool(lib().sk_options_get_use_inner_iterations(self._h))
+        def setInnerIterationTolerance(self, v): self._set("inner_iteration_tolerance", float(v))
+        def innerIterationTolerance(self): return lib().sk_options_get_inner_iteration_tolerance(self._h)
+
+        def setInnerIterationOrdering(self, ordering):
+            """The groups of the inner iterations: an ordered-groups-like object — anything with groupToElements() returning
+            {group id: parameter blocks}, such a dict itself, or (block, group id) pairs; None or empty: automatic.  A block is
+            a DoubleArray (params.slice(offset)).  Blocks that are not listed are not refined."""
+            if ordering is not None and hasattr(ordering, "groupToElements"):
+                ordering = ordering.groupToElements()
+            if isinstance(ordering, dict):
+                ordering = [(blk, g) for g in sorted(ordering) for blk in ordering[g]]
+            pairs = list(ordering or [])
+            self._keep.append([blk for blk, _ in pairs])
+            ptrs = (_dp * max(len(pairs), 1))(*[C.cast(blk.cast(), _dp) for blk, _ in pairs])
+            groups = np.array([int(g) for _, g in pairs] or [0], dtype=np.int32)
+            _check_arg(lib().sk_options_set_inner_iteration_ordering(self._h, ptrs, groups.ctypes.data_as(_ip), len(pairs)))
 
         def setCholeskyTuning(self, group=0, lookahead=True):
             _check(lib().sk_options_set_cholesky_tuning(self._h, int(group), int(bool(lookahead))))
@@ -1558,7 +1599,7 @@ class Solver:
         def iterations(self):
             names = ["cost", "cost_change", "gradient_max_norm", "step_norm", "relative_decrease",
                      "trust_region_radius", "step_is_valid", "step_is_successful", "step_size", "line_search_evaluations",
-                     "linear_solver_iterations"]
+                     "linear_solver_iterations", "inner_iteration_rounds"]
             return [{nm: lib().sk_summary_iteration_field(self._h, i, k) for k, nm in enumerate(names)}
                     for i in range(lib().sk_summary_num_logged_iterations(self._h))]
 
@@ -1617,6 +1658,14 @@ class StepSolver:
         v = C.c_double()
         _check(lib().sk_solver_stat(self._h, name.encode(), C.byref(v)))
         return v.value
+
+    def innerIterationBlocks(self):
+        """Per parameter block the iterations and the status of its inner solve in the last refinement (-1: not refined)
+        (sk_solver_inner_iteration_blocks): (iterations, status) as int arrays."""
+        nb = lib().sk_problem_num_parameter_blocks(self._keep[1]._h)
+        it, st = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.int32)
+        _check_arg(lib().sk_solver_inner_iteration_blocks(self._h, it.ctypes.data_as(_ip), st.ctypes.data_as(_ip)))
+        return it[:nb].copy(), st[:nb].copy()
 
     def distribution(self):
         """("sharded" | "replicated", measured all-reduce seconds, estimated seconds of work sharding removes per iteration)."""

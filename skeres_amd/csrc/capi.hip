@@ -9,6 +9,7 @@
 #include "dense_rows_kernels.hpp"
 #include "evaluate_kernels.hpp"
 #include "cgnr_plan.hpp"
+#include "inner_plan.hpp"
 #include "covariance.hpp"
 #include "covariance_plan.hpp"
 #include "evaluate_plan.hpp"
@@ -82,6 +83,7 @@ const DevKnobs& dev_knobs() {
     k.dissect_at = num("SK_DISSECT_AT", -1);
     k.schedule_plain = num("SK_SCHEDULE_PLAIN", 0);
     k.cgnr_batch = num("SK_CGNR_BATCH", 0);
+    k.inner_batch = num("SK_INNER_BATCH", 0);
     k.chain_xcd_local = num("SK_CHAIN_XCD_LOCAL", 0);
     if (const char* e = getenv("SK_BS_PAIR")) k.bs_pair = atoi(e);
     if (const char* e = getenv("SK_BS_SPREAD")) k.bs_spread = atoi(e);
@@ -813,6 +815,53 @@ int sk_cgnr_elimination_plan(const sk_problem* p, int* eliminated_of_block, int*
   return SK_OK;
   SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
+int sk_options_set_use_inner_iterations(sk_options* o, int on) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.use_inner_iterations = on != 0; return SK_OK;
+}
+int sk_options_get_use_inner_iterations(const sk_options* o) { return o && o->o.use_inner_iterations ? 1 : 0; }
+int sk_options_set_inner_iteration_tolerance(sk_options* o, double v) {
+  if (!o) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  if (!(v >= 0.0)) { set_error("inner_iteration_tolerance must be >= 0"); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.inner_iteration_tolerance = v; return SK_OK;
+}
+double sk_options_get_inner_iteration_tolerance(const sk_options* o) { return o ? o->o.inner_iteration_tolerance : NAN; }
+int sk_options_set_inner_iteration_ordering(sk_options* o, double* const* blocks, const int* groups, int n) {
+  SK_GUARD_BEGIN
+  if (!o || n < 0 || (n > 0 && (!blocks || !groups))) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
+  for (int i = 0; i < n; ++i) if (groups[i] < 0) { set_error("inner_iteration_ordering: entry %d has the negative group id %d", i, groups[i]); return SK_ERR_INVALID_ARGUMENT; }
+  o->o.inner_ordering_blocks.assign(blocks, blocks + n); o->o.inner_ordering_groups.assign(groups, groups + n);
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+// The inner plan of these options on this problem, from host data alone
+static int inner_plan_of(const Problem& p, const Options* o, InnerPlan* inner, CgnrPlan* plan) {
+  std::string why;
+  int rc = cgnr_plan_build(p, plan, &why, false);
+  if (rc == SK_OK) {
+    static const std::vector<double*> no_blocks; static const std::vector<int> no_groups;
+    rc = inner_plan_build(p, *plan, o ? o->inner_ordering_blocks : no_blocks, o ? o->inner_ordering_groups : no_groups, inner, &why);
+  }
+  if (rc != SK_OK) set_error("%s", why.c_str());
+  return rc;
+}
+int sk_inner_iteration_plan(const sk_problem* p, const sk_options* o, int* group_of_block, int* num_groups) {
+  SK_GUARD_BEGIN
+  if (!p) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  const std::string refusal = cgnr_refusal(p->p, 1, false);
+  if (!refusal.empty()) { set_error("%s", refusal.c_str()); return SK_ERR_UNSUPPORTED; }
+  CgnrPlan plan;
+  InnerPlan inner;
+  const int rc = inner_plan_of(p->p, o ? &o->o : nullptr, &inner, &plan);
+  if (rc != SK_OK) return rc;
+  if (group_of_block) {
+    for (size_t b = 0; b < p->p.block_ptr.size(); ++b) group_of_block[b] = -1;
+    for (size_t c = 0; c < plan.cols.cb_block.size(); ++c) group_of_block[plan.cols.cb_block[c]] = inner.group_of_cb[c];
+  }
+  if (num_groups) *num_groups = (int)inner.groups.size();
+  return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
 int sk_options_set_eta(sk_options* o, double v) {
   if (!(v > 0.0 && v < 1.0)) { set_error("eta must lie inside (0, 1)"); return SK_ERR_INVALID_ARGUMENT; }
   o->o.eta = v; return SK_OK;
@@ -906,6 +955,7 @@ double sk_summary_iteration_field(const sk_summary* s, int it, int field) {
     case 0: return L.cost; case 1: return L.cost_change; case 2: return L.gradient_max_norm; case 3: return L.step_norm;
     case 4: return L.relative_decrease; case 5: return L.trust_region_radius; case 6: return L.step_is_valid; case 7: return L.step_is_successful;
     case 8: return L.step_size; case 9: return L.line_search_evaluations; case 10: return L.linear_solver_iterations;
+    case 11: return L.inner_iteration_rounds;
   }
   return NAN;
 }
@@ -916,6 +966,10 @@ double sk_summary_phase_seconds(const sk_summary* s, int phase) { return (phase 
 // ---- solve ------------------------------------------------------------------------------
 static std::unique_ptr<SolverBase> make_solver(const Options& o, Problem* p, int* rc) {
   *rc = SK_OK;
+  if (o.use_inner_iterations) {  // (from the options alone: before any device is touched)
+    const std::string refusal = inner_refusal(o.linear_solver_type, linear_solver_name(o.linear_solver_type));
+    if (!refusal.empty()) { set_error("%s", refusal.c_str()); *rc = SK_ERR_UNSUPPORTED; return nullptr; }
+  }
   if (p->has_parameterization() && o.linear_solver_type != SK_DENSE_SCHUR && problem_is_dense_rows(*p)) {
     set_error("local parameterizations and constant parameter blocks are implemented for residual-block problems (DENSE_QR / DENSE_NORMAL_CHOLESKY; identity, subset and constant blocks under DENSE_SCHUR), not for dense rows (not supported here)");
     *rc = SK_ERR_UNSUPPORTED; return nullptr;
@@ -923,6 +977,12 @@ static std::unique_ptr<SolverBase> make_solver(const Options& o, Problem* p, int
   if (o.linear_solver_type == SK_CGNR) {  // every shape it takes, bundle adjustment included: the full system, or the implicit Schur complement (sk_options_set_schur_elimination)
     const std::string refusal = cgnr_refusal(*p, o.world, o.trust_region_strategy_type == SK_DOGLEG);  // (host data alone: before any device is touched)
     if (!refusal.empty()) { set_error("%s", refusal.c_str()); *rc = SK_ERR_UNSUPPORTED; return nullptr; }
+    if (o.use_inner_iterations && !o.inner_ordering_blocks.empty()) {  // the caller's ordering, checked from host data as well
+      CgnrPlan plan;
+      InnerPlan inner;
+      *rc = inner_plan_of(*p, &o, &inner, &plan);
+      if (*rc != SK_OK) return nullptr;
+    }
     return make_cgnr_solver(o, p);
   }
   if (o.linear_solver_type == SK_DENSE_SCHUR) {
@@ -998,6 +1058,13 @@ int sk_solver_stat(const sk_solver* s, const char* name, double* value) {
   if (strncmp(name, "phase_seconds_", 14) == 0 && name[14] >= '0' && name[14] <= '5' && !name[15]) { *value = s->impl->phase_seconds(name[14] - '0'); return SK_OK; }
   if (!s->impl->stat(name, value)) { set_error("this solver reports no figure named '%s'", name); return SK_ERR_INVALID_ARGUMENT; }
   return SK_OK;
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
+}
+
+int sk_solver_inner_iteration_blocks(sk_solver* s, int* iterations, int* status) {
+  SK_GUARD_BEGIN
+  if (!s) { set_error("null argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return s->impl->inner_blocks(iterations, status);
   SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
 

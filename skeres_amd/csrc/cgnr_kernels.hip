@@ -38,7 +38,8 @@ __device__ inline double block_max_256(double v, double* sh) {
 // ---- block sums -------------------------------------------------------------------------------------------------------------------
 // One wave per part: lane e (e, e + 64, ... below size^2) owns entry (a, b) of the block's matrix and walks the part's slots in plan
 // order.  A long block's parts are summed entry by entry, in part order, by the second launch.
-__global__ __launch_bounds__(64) void cgnr_block_diag_kernel(CgnrJac J, CgnrCols C, double* bsum, double* partial) {
+__global__ __launch_bounds__(64) void cgnr_block_diag_kernel(CgnrJac J, CgnrCols C, double* bsum, double* partial, const int* flags) {
+  if (cg_done(flags)) return;
   const int part = blockIdx.x;
   const int c = C.part_cb[part], size = C.cb_size[c], begin = C.part_begin[part], end = C.part_end[part], out = C.part_out[part];
   for (int e = threadIdx.x; e < size * size; e += 64) {
@@ -54,7 +55,8 @@ __global__ __launch_bounds__(64) void cgnr_block_diag_kernel(CgnrJac J, CgnrCols
     if (out < 0) bsum[C.cb_moff[c] + e] = s; else partial[(size_t)out * 256 + e] = s;
   }
 }
-__global__ __launch_bounds__(64) void cgnr_block_diag_long_kernel(CgnrCols C, double* bsum, const double* partial) {
+__global__ __launch_bounds__(64) void cgnr_block_diag_long_kernel(CgnrCols C, double* bsum, const double* partial, const int* flags) {
+  if (cg_done(flags)) return;
   const int c = C.long_cb[blockIdx.x], size = C.cb_size[c];
   const int begin = C.long_begin[blockIdx.x], end = C.long_begin[blockIdx.x + 1];
   for (int e = threadIdx.x; e < size * size; e += 64) {
@@ -63,9 +65,9 @@ __global__ __launch_bounds__(64) void cgnr_block_diag_long_kernel(CgnrCols C, do
     bsum[C.cb_moff[c] + e] = s;
   }
 }
-void launch_cgnr_block_diag(const CgnrJac& J, const CgnrCols& C, double* bsum, double* partial, hipStream_t s) {
-  if (C.num_parts > 0) hipLaunchKernelGGL(cgnr_block_diag_kernel, dim3(C.num_parts), dim3(64), 0, s, J, C, bsum, partial);
-  if (C.num_long > 0) hipLaunchKernelGGL(cgnr_block_diag_long_kernel, dim3(C.num_long), dim3(64), 0, s, C, bsum, (const double*)partial);
+void launch_cgnr_block_diag(const CgnrJac& J, const CgnrCols& C, double* bsum, double* partial, hipStream_t s, const int* flags) {
+  if (C.num_parts > 0) hipLaunchKernelGGL(cgnr_block_diag_kernel, dim3(C.num_parts), dim3(64), 0, s, J, C, bsum, partial, flags);
+  if (C.num_long > 0) hipLaunchKernelGGL(cgnr_block_diag_long_kernel, dim3(C.num_long), dim3(64), 0, s, C, bsum, (const double*)partial, flags);
 }
 
 // ---- Jacobi scaling ---------------------------------------------------------------------------------------------------------------

@@ -46,7 +46,8 @@ constexpr int kCgnrBlockChunk = 256;  // column blocks per first-stage workgroup
 
 // --- after an evaluation -----------------------------------------------------------------------------------------------------------
 // bsum[cb_moff[c] + a * size + b] = sum over the block's slots of (J_slot^T J_slot)(a, b); partial: [num_partials * 256]
-void launch_cgnr_block_diag(const CgnrJac& J, const CgnrCols& C, double* bsum, double* partial, hipStream_t s);
+// flags (may be null): the done flag of whoever enqueues ahead (the inner iterations: inner_iterations.hip)
+void launch_cgnr_block_diag(const CgnrJac& J, const CgnrCols& C, double* bsum, double* partial, hipStream_t s, const int* flags = nullptr);
 // scale_j = 1 / (1 + sqrt(bsum's diagonal)) — iteration 0, from the sums of the unscaled Jacobian
 void launch_cgnr_scale_compute(const CgnrCols& C, const double* bsum, double* scale, hipStream_t s);
 // values <- values diag(scale), in place

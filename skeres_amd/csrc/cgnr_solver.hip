@@ -18,6 +18,13 @@
 // JACOBI is then the block diagonal of S (cgnr_schur_diag_kernel), formed once per linear solve because the radius changes V.
 // The vectors keep the full tangent space's columns; the entries of E stay zero until the back-substitution.  Without the option
 // the launches are the ones above, unchanged.
+//
+// Inner iterations (sk_options_set_use_inner_iterations; inner_iterations.hpp).  The component is handed this solver's device
+// Jacobian, values array, staging and residual and cost-term arrays, and refines the candidate x_new_ in place.  Its rounds read and
+// leave the values UNSCALED, at points other than x.  So nothing of a refinement is copied: when the refined step is rejected, the
+// next linear solve begins with the evaluation launches at x again (values, residuals, cost terms) and the scaling in place —
+// the same launches on the same point, hence the same bytes as before; an accepted step evaluates at the new point anyway.  The
+// sums, the gradient and the scalars of x are not touched by a refinement (it has buffers of its own for a block's g and H).
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -25,6 +32,7 @@
 #include "cgnr_kernels.hpp"
 #include "cgnr_plan.hpp"
 #include "evaluate_kernels.hpp"
+#include "inner_iterations.hpp"
 #include "jacobian_device.hpp"
 #include "solver.hpp"
 
@@ -45,12 +53,18 @@ class CgnrSolver : public SolverBase {
   int linear_solve(double radius, LinearSolve* out) override;
   const char* refuses_bounds() const override { return "parameter bounds under CGNR are not supported (DENSE_SCHUR and DENSE_QR / DENSE_NORMAL_CHOLESKY take them)"; }
   void accept_candidate() override { std::swap(x_, x_new_); }
+  int refine_candidate(double* cost, double* step_norm, int* rounds, bool* ok) override;
   int write_back() override;
   void describe(Summary* s) override {
     s->num_parameter_blocks = (int)problem_->block_size.size();
     s->num_parameters = plan_.cols.num_ambient; s->num_residual_blocks = (int)problem_->rb_functor.size(); s->num_residuals = plan_.eval.num_rows;
     s->preconditioner_type = opt_.preconditioner_type; s->linear_solver_iterations = n_cg_iterations_;
     s->schur_elimination = schur(); s->eliminated_blocks = (int)plan_.E.cb.size(); s->reduced_columns = plan_.reduced_cols;
+    s->inner_iteration_groups = (int)inner_plan_.groups.size();
+  }
+  int inner_blocks(int* iterations, int* status) override {
+    if (!opt_.use_inner_iterations) { set_error("use_inner_iterations is off"); return SK_ERR_INVALID_ARGUMENT; }
+    return inner_.blocks(iterations, status);
   }
   bool stat(const std::string& name, double* value) const override {
     if (name == "cg_iterations") { *value = (double)n_cg_iterations_; return true; }
@@ -58,6 +72,7 @@ class CgnrSolver : public SolverBase {
     if (name == "cg_status_last") { *value = (double)cg_status_last_; return true; }
     if (name == "cg_batches") { *value = (double)n_batches_; return true; }
     if (name == "jacobian_nonzeros") { *value = (double)plan_.eval.num_nonzeros; return true; }
+    if (name == "inner_iteration_groups") { *value = (double)inner_plan_.groups.size(); return true; }
     if (name == "graph_replay") { *value = 0.0; return true; }
     if (name == "schur_elimination") { *value = schur() ? 1.0 : 0.0; return true; }
     if (name == "eliminated_blocks") { *value = (double)plan_.E.cb.size(); return true; }
@@ -85,6 +100,11 @@ class CgnrSolver : public SolverBase {
   }
 
   CgnrPlan plan_;
+  InnerPlan inner_plan_;
+  InnerIterations inner_;
+  DevBuf<double> b_x_unrefined_;
+  bool values_stale_ = false;  // a refinement has overwritten values, residuals and cost terms of x: evaluate again before they are read
+  int restore_jacobian();
   int n_ = 0, ng_ = 0, m_ = 0, nb_ = 0, num_pb_ = 0, update_parts_ = 0;
   DeviceJacobian dj_;  // the problem and the evaluation's plan on the device (uploaded once); its x is the starting point
   // the solver's plan on the device
@@ -124,6 +144,10 @@ int CgnrSolver::setup() {
   std::string why;
   int rc = cgnr_plan_build(p, &plan_, &why, schur());
   if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
+  if (opt_.use_inner_iterations) {
+    rc = inner_plan_build(p, plan_, opt_.inner_ordering_blocks, opt_.inner_ordering_groups, &inner_plan_, &why);
+    if (rc != SK_OK) { set_error("%s", why.c_str()); return rc; }
+  }
   const EvaluatePlan& E = plan_.eval;
   const TangentColumns& T = plan_.cols;
   const PartList& L = plan_.parts;
@@ -164,7 +188,7 @@ int CgnrSolver::setup() {
   const int ncb = (int)T.cb_col.size();
   update_parts_ = (ncb + kCgnrBlockChunk - 1) / kCgnrBlockChunk;
   const size_t parts = std::max({(size_t)3 * update_parts_, (size_t)(n_ / kCgnrDotChunk + 1), (size_t)(m_ / kCgnrDotChunk + 1), (size_t)(num_pb_ / 256 + 1),
-                                 (size_t)(nb_ / kEvaluateSumChunk + 1)});
+                                 (size_t)(nb_ / kEvaluateSumChunk + 1), (size_t)(ng_ / kCgnrDotChunk + 1)});
   SK_HIP_TRY(b_part_.alloc(parts));
   SK_HIP_TRY(b_jtw_part_.alloc(std::max<size_t>((size_t)L.num_partials * kCgnrLanes, 1)));
   SK_HIP_TRY(b_bd_part_.alloc(std::max<size_t>((size_t)L.num_partials * 256, 1)));
@@ -181,6 +205,15 @@ int CgnrSolver::setup() {
   cols_.long_cb = b_long_cb_.p; cols_.long_begin = b_long_begin_.p;
   cg_jac_ = jac_; cg_cols_ = cols_; b_rhs_ = b_b_.p; cg_update_parts_ = update_parts_;
   if (schur()) { rc = setup_schur(); if (rc != SK_OK) return rc; }
+  if (opt_.use_inner_iterations) {
+    InnerIterations::Shared sh;
+    sh.dj = &dj_; sh.jac = jac_; sh.group_stage_cost = &plan_.group_stage_cost; sh.blk_stage_cost = b_blk_stage_cost_.p;
+    sh.r = b_r_.p; sh.rc = b_rc_.p; sh.cterm = b_cterm_.p; sh.cterm_c = b_cterm_c_.p; sh.jtw_partial = b_jtw_part_.p; sh.bd_partial = b_bd_part_.p;
+    sh.num_cols = n_; sh.num_ambient = ng_; sh.num_pb = num_pb_; sh.matrix_entries = msize;
+    rc = inner_.setup(inner_plan_, sh, s);
+    if (rc != SK_OK) return rc;
+    SK_HIP_TRY(b_x_unrefined_.alloc((size_t)ng_));
+  }
   SK_HIP_TRY(hipStreamSynchronize(s));
   return SK_OK;
 }
@@ -239,8 +272,47 @@ void CgnrSolver::finish(const double* x_dev, bool jac) {
   else dj_.finish(x_dev, b_rc_.p, nullptr, b_cterm_c_.p, b_blk_stage_cost_.p);
 }
 
+// After a refinement whose step was rejected: values, residuals and cost terms of x again, as evaluate_with_jacobian left them.
+int CgnrSolver::restore_jacobian() {
+  int rc = evaluate(x_, true);
+  if (rc) return rc;
+  finish(x_, true);
+  if (opt_.jacobi_scaling) launch_cgnr_scale_apply(jac_, b_scale_.p, stream_);
+  values_stale_ = false;
+  return SK_OK;
+}
+
+// The candidate x_new_ refined in place, its cost by the cost launches of linear_solve, |x - x_new_|.
+int CgnrSolver::refine_candidate(double* cost, double* step_norm, int* rounds, bool* ok) {
+  hipStream_t s = stream_;
+  *ok = false;
+  SK_HIP_TRY(hipMemcpyAsync(b_x_unrefined_.p, x_new_, (size_t)ng_ * sizeof(double), hipMemcpyDeviceToDevice, s));
+  values_stale_ = true;
+  int rc = inner_.refine(x_new_, rounds);
+  if (rc) return rc;
+  SK_HIP_TRY(hipMemsetAsync(dj_.fail_flag(), 0, sizeof(int), s));
+  rc = evaluate(x_new_, false);
+  if (rc) return rc;
+  finish(x_new_, false);
+  launch_evaluate_cost(b_cterm_c_.p, nb_, b_part_.p, b_scal_.p + kCgCandCost, s);
+  launch_inner_diff_sq(x_, x_new_, ng_, b_part_.p, s);
+  launch_cgnr_sum(b_part_.p, (ng_ + kCgnrDotChunk - 1) / kCgnrDotChunk, b_scal_.p + kCgStepSq, nullptr, s);
+  SK_HIP_TRY(hipMemcpyAsync(h_scal_, b_scal_.p, kCgScalCount * sizeof(double), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipMemcpyAsync(h_flags_ + kCgFlagCount, dj_.fail_flag(), sizeof(int), hipMemcpyDeviceToHost, s));
+  SK_HIP_TRY(hipStreamSynchronize(s));
+  SK_HIP_TRY(hipGetLastError());
+  if (h_flags_[kCgFlagCount] || !std::isfinite(h_scal_[kCgCandCost]) || !std::isfinite(h_scal_[kCgStepSq])) {
+    SK_HIP_TRY(hipMemcpyAsync(x_new_, b_x_unrefined_.p, (size_t)ng_ * sizeof(double), hipMemcpyDeviceToDevice, s));
+    SK_HIP_TRY(hipStreamSynchronize(s));
+    return SK_OK;
+  }
+  *ok = true; *cost = h_scal_[kCgCandCost]; *step_norm = std::sqrt(h_scal_[kCgStepSq]);
+  return SK_OK;
+}
+
 int CgnrSolver::evaluate_with_jacobian(bool first) {
   hipStream_t s = stream_;
+  values_stale_ = false;
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   SK_HIP_TRY(hipMemsetAsync(dj_.fail_flag(), 0, sizeof(int), s));
   int rc = evaluate(x_, true);
@@ -299,6 +371,7 @@ int CgnrSolver::linear_solve(double radius, LinearSolve* out) {
   ++n_linear_solves_;
   const int max_it = opt_.max_linear_solver_iterations;
   const int batch = dev_knobs().cgnr_batch > 0 ? dev_knobs().cgnr_batch : cgnr::kBatch;
+  if (values_stale_) { const int rc = restore_jacobian(); if (rc) return rc; }
   SK_HIP_TRY(hipEventRecord(ev_[kEvBegin], s));
   SK_HIP_TRY(hipMemsetAsync(b_flags_.p, 0, kCgFlagCount * sizeof(int), s));
   launch_cgnr_precond_factor(cols_, b_bsum_.p, opt_.min_lm_diagonal, opt_.max_lm_diagonal, radius, b_D2_.p, jacobi() || schur() ? b_L_.p : nullptr, b_flags_.p, s);

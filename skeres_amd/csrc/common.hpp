@@ -86,6 +86,11 @@ struct Options {  // Solver.Options; Ceres 1.x defaults
   double eta = 0.1;
   int max_linear_solver_iterations = 500, min_linear_solver_iterations = 0;
   bool cgnr_schur_elimination = false;  // sk_options_set_schur_elimination: CG on the implicit Schur complement of an independent set (cgnr_plan.hpp)
+  // Inner iterations (common.hpp: namespace inner; inner_plan.hpp): off by default; the ordering's blocks with a group id each (empty: automatic)
+  bool use_inner_iterations = false;
+  double inner_iteration_tolerance = 1e-3;
+  std::vector<double*> inner_ordering_blocks;
+  std::vector<int> inner_ordering_groups;
   int device = -1;
   hipStream_t stream = nullptr;
   bool stream_set = false;
@@ -147,6 +152,20 @@ constexpr int kPartSlots = 64;            // a column block's slot list is summe
 enum Status { kConverged = 0, kIterationLimit = 1, kBreakdown = 2, kZeroRhs = 3, kRunning = -1 };
 }  // namespace cgnr
 
+// Inner iterations: Ceres 1.x's use_inner_iterations (block coordinate descent behind every trust-region step), recalled, not
+// pinned (like SURVEY.md §8a row a13), so the constants live here and nowhere else.  One inner solve is the Levenberg-Marquardt
+// loop of SolverBase::step on one parameter block with Ceres' DEFAULT options, whatever the outer solve's options are.
+namespace inner {
+constexpr int kMaxNumIterations = 50;
+constexpr double kFunctionTolerance = 1e-6, kGradientTolerance = 1e-10, kParameterTolerance = 1e-8;
+constexpr double kInitialRadius = 1e4, kMaxRadius = 1e16, kMinRadius = 1e-32;
+constexpr double kMinRelativeDecrease = 1e-3, kMinLmDiagonal = 1e-6, kMaxLmDiagonal = 1e32;
+constexpr int kMaxConsecutiveInvalidSteps = 5;
+constexpr int kBatch = 4;  // rounds enqueued between two reads of the group's done flag (SK_INNER_BATCH)
+// how a block's solve ended ("status" of sk_solver_inner_iteration_blocks); kRunning while it goes on
+enum Status { kRunning = 0, kGradient = 1, kParameter = 2, kFunction = 3, kIterationLimit = 4, kInvalidSteps = 5, kRadius = 6 };
+}  // namespace inner
+
 struct IterationLog {
   int iteration = 0;
   double cost = 0, cost_change = 0, gradient_max_norm = 0, step_norm = 0, relative_decrease = 0,
@@ -155,6 +174,7 @@ struct IterationLog {
   double step_size = 1.0;           // the line search's alpha under parameter bounds
   int line_search_evaluations = 1;  // candidate costs evaluated in the iteration
   int linear_solver_iterations = 0; // CGNR: CG iterations of the iteration's linear solve (0 for the factorisation solvers)
+  int inner_iteration_rounds = 0;   // use_inner_iterations: the lock-step rounds that refined this iteration's candidate
 };
 
 struct Summary {
@@ -176,6 +196,11 @@ struct Summary {
   long linear_solver_iterations = 0;    // CGNR: total over the solve
   bool schur_elimination = false;       // CGNR with sk_options_set_schur_elimination: the eliminated blocks and the columns CG runs on
   int eliminated_blocks = 0, reduced_columns = 0;
+  bool use_inner_iterations = false;    // the report's inner-iterations lines appear with the option on alone
+  int inner_iteration_groups = 0, inner_iteration_steps = 0;
+  long inner_iteration_rounds = 0;
+  bool inner_iterations_enabled = false;
+  double inner_iteration_seconds = 0.0;
   std::string device_name;
   std::string brief, full;
   void build_reports();

@@ -24,6 +24,7 @@ struct DevKnobs {
   int bulk_reserve = -1, bulk_reserve_early = -1;  // SK_BULK_RESERVE=<a>[,<b>]: CUs per XCD kept free of the SYRKs on the bulk / early-bulk streams (sweeps; default 4, 2)
   int chain_xcd_local = 0;         // SK_CHAIN_XCD_LOCAL=1: the resident chain's critical hand-overs through the potrf server's XCD's L2 instead of device-scope counters (round 5: pays on one front, not on two in lock-step)
   int cgnr_batch = 0;              // SK_CGNR_BATCH=<k>: CG iterations enqueued between two reads of the done flag (0: cgnr::kBatch) — the same bytes for every k
+  int inner_batch = 0;             // SK_INNER_BATCH=<k>: inner-iteration rounds enqueued between two reads of the done flag (0: inner::kBatch) — the same bytes for every k
   int schedule_plain = 0;          // SK_SCHEDULE_PLAIN=1: the envelope zeroed in line and the pair kernels in plain block order (the schedule-independence test)
 };
 const DevKnobs& dev_knobs();

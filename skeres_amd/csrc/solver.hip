@@ -70,6 +70,10 @@ bool SolverBase::strategy_stat(const std::string& name, double* value) const {
   if (name == "bounded_coordinates") { *value = (double)bounded_coordinates_; return true; }
   if (name == "active_bounds") { *value = (double)active_bounds_; return true; }
   if (name == "line_search_evaluations") { *value = (double)n_ls_evals_; return true; }
+  if (name == "inner_iteration_steps") { *value = (double)inner_steps_; return true; }
+  if (name == "inner_iteration_rounds") { *value = (double)inner_rounds_; return true; }
+  if (name == "inner_iterations_enabled") { *value = opt_.use_inner_iterations && inner_enabled_ ? 1.0 : 0.0; return true; }
+  if (name == "inner_iteration_seconds") { *value = inner_seconds_; return true; }
   if (name == "linear_solves") { *value = (double)n_linear_solves_; return true; }
   if (name == "dogleg_reused_steps") { *value = (double)n_dl_reused_; return true; }
   if (name == "dogleg_mu") { *value = dl_mu_; return true; }
@@ -159,6 +163,7 @@ void SolverBase::log_iteration(int it, double cost_change, double step_norm, dou
   L.step_is_valid = valid; L.step_is_successful = success; L.iter_time = iter_time; L.total_time = now();
   L.step_size = ls_alpha_; L.line_search_evaluations = ls_evals_;
   L.linear_solver_iterations = it == 0 ? 0 : cg_iterations_last_;
+  L.inner_iteration_rounds = it == 0 ? 0 : inner_rounds_last_;
   sum_.iterations.push_back(L);
   if (opt_.progress_to_stdout && opt_.rank == 0) {
     if (it == 0) printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius  ls_iter  iter_time  total_time\n");
@@ -325,7 +330,7 @@ int SolverBase::step(bool* done) {
   }
   const double t_iter = now();
   ++iteration_;
-  ls_alpha_ = 1.0; ls_evals_ = 1; cg_iterations_last_ = 0;
+  ls_alpha_ = 1.0; ls_evals_ = 1; cg_iterations_last_ = 0; inner_rounds_last_ = 0;
   bool valid = false;
   double mcc = 0.0, new_cost = 0.0, step_norm = 0.0;
   int rc = try_step(radius_, &valid, &mcc, &new_cost, &step_norm);
@@ -347,6 +352,21 @@ int SolverBase::step(bool* done) {
     return SK_OK;
   }
   invalid_ = 0;
+  bool useful = false;
+  if (opt_.use_inner_iterations && inner_enabled_ && std::isfinite(new_cost)) {  // (a candidate without a cost is not refined: nothing to start from)
+    const double t_inner = now(), c_tr = new_cost;
+    double c_in = 0.0, norm_in = 0.0;
+    bool ok = false;
+    rc = refine_candidate(&c_in, &norm_in, &inner_rounds_last_, &ok);
+    if (rc) return rc;
+    inner_seconds_ += now() - t_inner; ++inner_steps_; inner_rounds_ += inner_rounds_last_;
+    if (ok) {
+      mcc += c_tr - c_in;
+      useful = c_in < cost_;
+      inner_enabled_ = (1.0 - c_in / c_tr) > opt_.inner_iteration_tolerance;
+      new_cost = c_in; step_norm = norm_in;
+    }
+  }
   if (!std::isfinite(new_cost)) new_cost = std::numeric_limits<double>::max();
   const double cost_change = cost_ - new_cost;
   if (step_norm <= opt_.parameter_tolerance * (xnorm_ + opt_.parameter_tolerance)) {
@@ -364,7 +384,7 @@ int SolverBase::step(bool* done) {
     return SK_OK;
   }
   const double rho = cost_change / mcc;
-  if (rho > opt_.min_relative_decrease) {
+  if (rho > opt_.min_relative_decrease || useful) {
     accept_candidate();
     rc = evaluate_with_jacobian(false);
     if (rc == SK_ERR_EVALUATION_FAILED) {
@@ -406,6 +426,8 @@ int SolverBase::finish(Summary* s) {
   sum_.world = opt_.world;
   sum_.linear_solver_type = opt_.linear_solver_type;
   sum_.linear_solver_type_given = opt_.linear_solver_type_given;
+  sum_.use_inner_iterations = opt_.use_inner_iterations; sum_.inner_iteration_steps = inner_steps_; sum_.inner_iteration_rounds = inner_rounds_;
+  sum_.inner_iterations_enabled = opt_.use_inner_iterations && inner_enabled_; sum_.inner_iteration_seconds = inner_seconds_;
   describe(&sum_);
   sum_.build_reports();
   *s = sum_;
@@ -441,6 +463,11 @@ void Summary::build_reports() {
       snprintf(b, sizeof(b), "Schur elimination      implicit: %d blocks eliminated, %d reduced columns\n", eliminated_blocks, reduced_columns);
       f += b;
     }
+  }
+  if (use_inner_iterations) {
+    snprintf(b, sizeof(b), "Inner iterations       %d groups: %d steps refined in %ld rounds, %.6f s, %s at the end\n", inner_iteration_groups, inner_iteration_steps,
+             inner_iteration_rounds, inner_iteration_seconds, inner_iterations_enabled ? "enabled" : "switched off");
+    f += b;
   }
   if (linear_solver_type == SK_DENSE_SCHUR) {
     snprintf(b, sizeof(b), "Schur structure                        2,3,9\nE blocks (eliminated)       % 12d\nF blocks                    % 12d\n", num_e_blocks, num_f_blocks);

@@ -9,6 +9,13 @@
 // and its model, and a backtracking Armijo line search on cost(P(x + alpha delta)) (common.hpp: namespace bounds).  One
 // deliberate departure from Ceres' defaults: the line search interpolates quadratically from function values, not cubically
 // with a Jacobian at every trial point.
+// Inner iterations (Solver::Options::use_inner_iterations, CGNR): a valid candidate with a positive model cost change is refined
+// in place before the tolerance tests — every parameter block of an independent set minimised on its own, group after group
+// (inner_plan.hpp, inner_iterations.hpp; common.hpp: namespace inner).  With c the current cost, c_tr the candidate's and c_in
+// the refined candidate's: model_cost_change += c_tr - c_in, the step is successful when rho > min_relative_decrease OR
+// c_in < c, the radius update takes rho as it is, and the refinement switches itself off for the rest of the solve once
+// 1 - c_in / c_tr <= inner_iteration_tolerance.  A second departure from Ceres' defaults: the inner solves factor their (at most
+// 16 x 16) damped normal matrices by Cholesky where Ceres runs DENSE_QR.
 #pragma once
 #include <chrono>
 #include <memory>
@@ -60,6 +67,8 @@ class SolverBase {
   virtual double syrk_flops_per_solve() const { return 0.0; }
   virtual double syrk_c_bytes_per_solve() const { return 0.0; }  // C tiles read + written by those launches
   virtual bool stat(const std::string& name, double* value) const { (void)name; (void)value; return false; }  // sk_solver_stat
+  // sk_solver_inner_iteration_blocks: per parameter block the iterations and the inner::Status of its solve in the last refinement
+  virtual int inner_blocks(int* iterations, int* status) { (void)iterations; (void)status; set_error("this solver runs no inner iterations"); return SK_ERR_UNSUPPORTED; }
   bool dogleg() const { return opt_.trust_region_strategy_type == SK_DOGLEG; }
   // seconds accumulated so far in phase i (the summary's phase_seconds, readable between steps: "phase_seconds_<i>" of sk_solver_stat)
   // (between steps the stream is idle: the all-reduce phase takes in every collective's event pair first)
@@ -85,6 +94,14 @@ class SolverBase {
   virtual int dogleg_trial(double a, double b, double* cost, double* step_norm) { (void)a; (void)b; (void)cost; (void)step_norm; return SK_ERR_UNSUPPORTED; }
   // the candidate P(x + alpha delta) from the step of the last linear solve, its cost, |x - candidate|
   virtual int bounded_trial(double alpha, double* cost, double* step_norm) { (void)alpha; (void)cost; (void)step_norm; return SK_ERR_UNSUPPORTED; }
+  // use_inner_iterations: the candidate of the last linear solve refined in place.  *ok: *cost is the refined candidate's cost by the
+  // solver's own cost launches, *step_norm |x - refined candidate|; !*ok (the cost is not finite, or its evaluation failed): the
+  // unrefined candidate is back in place.  *rounds: the lock-step rounds it took.
+  virtual int refine_candidate(double* cost, double* step_norm, int* rounds, bool* ok) { (void)cost; (void)step_norm; (void)rounds; (void)ok; return SK_ERR_UNSUPPORTED; }
+  bool inner_enabled_ = true;       // inner_iterations_are_enabled: once false it stays false
+  int inner_steps_ = 0, inner_rounds_last_ = 0;  // iterations that were refined; the rounds of this iteration
+  long inner_rounds_ = 0;
+  double inner_seconds_ = 0.0;
   virtual void accept_candidate() = 0;            // x <- candidate (pointer swap)
   virtual int write_back() = 0;                   // device x -> caller memory
   virtual void describe(Summary* s) = 0;
@@ -135,6 +152,7 @@ class SolverBase {
   dogleg::Scalars dl_k_;            // the scalars of the last linear solve
   double dl_a_ = 0.0, dl_b_ = 0.0;  // the coefficients of the last step: a s + b g
   // "bounded_coordinates", "active_bounds", "line_search_evaluations";
+  // "inner_iteration_steps", "inner_iteration_rounds", "inner_iterations_enabled", "inner_iteration_seconds";
   // "linear_solves", "dogleg_reused_steps", "dogleg_mu"; under DOGLEG also dl_k_, dl_a_, dl_b_ as "dogleg_w_r", ..., "dogleg_b"
   bool strategy_stat(const std::string& name, double* value) const;
   Summary sum_;
