@@ -511,21 +511,23 @@ __global__ void lm_diagonal_kernel(const double* colsq, double* D, int n, double
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j < n) D[j] = sqrt(fmin(fmax(colsq[j], lo), hi) / radius);
 }
-// partial[0] = max |gs_j / scale_j| , partial[1] = sum x_j^2 over this block
+// partial[0] = max |gs_j / scale_j| , partial[1] = sum x_j^2 over this block.  The maximum keeps a NaN (max_keep_nan, common.hpp).  A column
+// with scale 0 AND gs 0 has no entry: a constant coordinate.  Scale 0 with any other gs is a column whose Jacobi scale 1 / (1 + inf)
+// vanished — an infinite Jacobian entry: its gs is inf * 0 = NaN and must be kept.
 __global__ __launch_bounds__(kBlock) void grad_max_xnorm_kernel(const double* gs, const double* scale, const double* x,
                                                                 int n, double* partial, int stride) {
   double m = 0.0, s = 0.0;
   for (int j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
-    if (scale[j] != 0.0) m = fmax(m, fabs(gs[j] / scale[j]));  // (a constant coordinate has no gradient entry)
+    if (scale[j] != 0.0 || gs[j] != 0.0) m = max_keep_nan(m, fabs(gs[j] / scale[j]));
     s += x[j] * x[j];
   }
   __shared__ double shm[kBlock / 64], shs[kBlock / 64];
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { m = fmax(m, __shfl_xor(m, off, 64)); s += __shfl_xor(s, off, 64); }
+  for (int off = 32; off > 0; off >>= 1) { m = max_keep_nan(m, __shfl_xor(m, off, 64)); s += __shfl_xor(s, off, 64); }
   if ((threadIdx.x & 63) == 0) { shm[threadIdx.x >> 6] = m; shs[threadIdx.x >> 6] = s; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    for (int i = 1; i < kBlock / 64; ++i) { m = fmax(m, shm[i]); s += shs[i]; }
+    for (int i = 1; i < kBlock / 64; ++i) { m = max_keep_nan(m, shm[i]); s += shs[i]; }
     partial[blockIdx.x] = m;
     partial[stride + blockIdx.x] = s;
   }
@@ -540,12 +542,12 @@ __global__ __launch_bounds__(kBlock) void final_reduce_kernel(const double* part
   double a = 0.0;
   for (int i = threadIdx.x; i < count; i += kBlock) {
     const double v = partial[(size_t)k * stride + i];
-    a = is_max ? fmax(a, v) : a + v;
+    a = is_max ? max_keep_nan(a, v) : a + v;
   }
   sh[threadIdx.x] = a;
   __syncthreads();
   for (int w = kBlock / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] = is_max ? fmax(sh[threadIdx.x], sh[threadIdx.x + w]) : sh[threadIdx.x] + sh[threadIdx.x + w];
+    if ((int)threadIdx.x < w) sh[threadIdx.x] = is_max ? max_keep_nan(sh[threadIdx.x], sh[threadIdx.x + w]) : sh[threadIdx.x] + sh[threadIdx.x + w];
     __syncthreads();
   }
   if (threadIdx.x == 0) out[k] = sh[0];
@@ -1056,11 +1058,11 @@ __global__ __launch_bounds__(1024) void final_reduce_rows_kernel(const double* p
   const bool is_max = rows.is_max[k] != 0;
   const double* src = partial + (size_t)rows.row[k] * stride;
   double a = 0.0;
-  for (int i = threadIdx.x; i < count; i += 1024) a = is_max ? fmax(a, src[i]) : a + src[i];  // (Venice-1778: 31 000 partial sums of the points)
+  for (int i = threadIdx.x; i < count; i += 1024) a = is_max ? max_keep_nan(a, src[i]) : a + src[i];  // (Venice-1778: 31 000 partial sums of the points)
   sh[threadIdx.x] = a;
   __syncthreads();
   for (int w = 512; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] = is_max ? fmax(sh[threadIdx.x], sh[threadIdx.x + w]) : sh[threadIdx.x] + sh[threadIdx.x + w];
+    if ((int)threadIdx.x < w) sh[threadIdx.x] = is_max ? max_keep_nan(sh[threadIdx.x], sh[threadIdx.x + w]) : sh[threadIdx.x] + sh[threadIdx.x + w];
     __syncthreads();
   }
   if (threadIdx.x == 0) *rows.out[k] = sh[0];

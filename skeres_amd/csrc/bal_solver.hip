@@ -1029,7 +1029,8 @@ int BalSolver::evaluate_with_jacobian(bool first) {
     // one process: cameras and points as ONE vector ([cameras | points] in every buffer), and the three reductions — sum r^2,
     // max |g|, |x|^2 — in one launch (round 4: five launches of ~6 us each became two)
     const int g = launch_grad_max_xnorm(b_gs_.p, b_scale_.p, d_.xc, (int)(nc + np), b_partial_.p + (size_t)partial_stride_, partial_stride_, s);
-    // (under bounds the gradient test is the projected gradient's: below, in a launch of its own — this one's maximum is not read)
+    // (under bounds the gradient test is the projected gradient's: below, in a launch of its own — this one's maximum is read for its
+    // finiteness alone: a Jacobian entry that is not finite fails the evaluation)
     // (kGradMaxPt and kXSqPt, the points' share in a world of ranks, stay zero: it is inside the cameras' slots here)
     ReduceRows rows;
     rows.n = 3;
@@ -1082,7 +1083,10 @@ int BalSolver::evaluate_with_jacobian(bool first) {
   gmax_ = segmented_ ? loc[1] : std::max(gmax_c, loc[1]);
   xnorm_ = std::sqrt((segmented_ ? 0.0 : x2_c) + loc[2]);
   if (bounded_) { gmax_ = h_scal_[kBounds + kBdGradMax]; active_bounds_ = (long)h_scal_[kBounds + kBdActive]; }
-  if (!std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
+  // (the maximum keeps a NaN on the device: a Jacobian entry that is not finite fails the evaluation like a residual that is not, as in Ceres.
+  // One device only: in a world of ranks a segment's maximum is its own, and a rank that failed alone would leave the others in the next
+  // collective; there the decision stays with the cost, which every rank has summed.)
+  if (!std::isfinite(cost_) || (!opt_.allreduce && (!std::isfinite(gmax_c) || !std::isfinite(loc[1])))) return SK_ERR_EVALUATION_FAILED;
   return SK_OK;
 }
 

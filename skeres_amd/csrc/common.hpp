@@ -21,6 +21,12 @@
 
 namespace sk {
 
+#ifdef __HIP__
+// A maximum that KEEPS a NaN (fmax drops it): a gradient entry that is not a number — a Jacobian entry that is not finite beside finite
+// residuals — must reach the host, where the evaluation fails on it (evaluate_with_jacobian: isfinite of the gradient max-norm).
+__device__ __forceinline__ double max_keep_nan(double a, double b) { return (b > a || b != b) ? b : a; }
+#endif
+
 void set_error(const char* fmt, ...);
 const char* get_error();
 void set_status(int status);  // status of the last failure that could only be reported as a null handle (sk_last_status)

@@ -393,15 +393,16 @@ __global__ __launch_bounds__(256) void dense_dogleg_combine_kernel(const double*
   for (int w = 128; w > 0; w >>= 1) { if (threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w]; __syncthreads(); }
   if (threadIdx.x == 0) out[0] = sh[0];
 }
-// out[0] = max_j |gs_j / scale_j| ; out[1] = |x|^2
+// out[0] = max_j |gs_j / scale_j| ; out[1] = |x|^2.  The maximum keeps a NaN (max_keep_nan, common.hpp): a gradient entry that is not a
+// number fails the evaluation on the host; a held column (0 / 0) has no entry.
 __global__ __launch_bounds__(256) void dense_gmax_kernel(const double* gs, const double* scale, const double* x, int n, double* out) {
   __shared__ double shm[256], shs[256];
   double mx = 0.0, s = 0.0;
-  for (int j = threadIdx.x; j < n; j += 256) { mx = fmax(mx, fabs(gs[j] / scale[j])); s += x[j] * x[j]; }
+  for (int j = threadIdx.x; j < n; j += 256) { if (scale[j] != 0.0 || gs[j] != 0.0) mx = max_keep_nan(mx, fabs(gs[j] / scale[j])); s += x[j] * x[j]; }
   shm[threadIdx.x] = mx; shs[threadIdx.x] = s;
   __syncthreads();
   for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) { shm[threadIdx.x] = fmax(shm[threadIdx.x], shm[threadIdx.x + w]); shs[threadIdx.x] += shs[threadIdx.x + w]; }
+    if (threadIdx.x < w) { shm[threadIdx.x] = max_keep_nan(shm[threadIdx.x], shm[threadIdx.x + w]); shs[threadIdx.x] += shs[threadIdx.x + w]; }
     __syncthreads();
   }
   if (threadIdx.x == 0) { out[0] = shm[0]; out[1] = shs[0]; }

@@ -161,7 +161,7 @@ int DenseRowsSolver::evaluate_with_jacobian(bool first) {
   SK_HIP_TRY(hipStreamSynchronize(s));
   add_phases(0, 0);
   cost_ = 0.5 * h_scal_[0]; gmax_ = h_scal_[1]; xnorm_ = std::sqrt(h_scal_[2]);
-  if (!std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
+  if (!std::isfinite(cost_) || !std::isfinite(gmax_)) return SK_ERR_EVALUATION_FAILED;
   return SK_OK;
 }
 

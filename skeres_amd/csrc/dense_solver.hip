@@ -310,7 +310,8 @@ int DenseSolver::evaluate_with_jacobian(bool first) {
   add_phases(0, 0);
   cost_ = 0.5 * h_scal_[kSumSq]; gmax_ = h_scal_[kGradMax]; xnorm_ = std::sqrt(h_scal_[kXSq]);
   if (bounded_) { gmax_ = h_scal_[kBounds + kBdGradMax]; active_bounds_ = (long)h_scal_[kBounds + kBdActive]; }
-  if (host_flag(kFail) || !std::isfinite(cost_)) return SK_ERR_EVALUATION_FAILED;
+  // (the unprojected maximum keeps a NaN: a Jacobian entry that is not finite fails the evaluation like a residual that is not, as in Ceres)
+  if (host_flag(kFail) || !std::isfinite(cost_) || !std::isfinite(h_scal_[kGradMax])) return SK_ERR_EVALUATION_FAILED;
   return SK_OK;
 }
 
