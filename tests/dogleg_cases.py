@@ -41,19 +41,44 @@ CASES = {
                                       options=dict(jacobi_scaling=False, initial_trust_region_radius=1.0)),
     "robust-radius-1": dict(shape=(16, 600, 2600), seed=11, perturb=DEFAULT_PERTURB, kmax=7, loss=("huber", 1.0), subset=True, const_pts=(5,),
                             options=dict(initial_trust_region_radius=1.0)),
+    # The mu loop (mu *= 10 while the damped system is not positive definite), which no case above reaches: the silent co-axial
+    # component of tests/failure_cases.py (case i there) appended to "plans".  Its free, exactly zero point columns have the diagonal
+    # min_lm_diagonal / (1 / mu) = 2^-1075 R* mu with R* = 2^12, which rounds to 0 — a zero pivot — exactly where R* mu <= 1: iteration 1
+    # fails at mu = 1e-8 .. 1e-4 (R* mu <= 0.41) and factors at 1e-3 (4.1); an accepted step sets mu = 2 mu / 10, so iteration 2 fails at
+    # 2e-4 (0.82) and factors at 2e-3, iteration 3 factors at 4e-4 (1.64) at once, iteration 4 fails at 8e-5 and factors at 8e-4: every
+    # decision at least 18 % from the threshold, where the roundings of mu and of 1 / mu are 1e-16.  No camera is held here: a held
+    # coordinate is inert, its diagonal under this min_lm_diagonal is subnormal, and wave_potrf32 takes the rcp of a camera pivot
+    # (tests/failure_cases.py says more); at mu >= 4e-4 the damping keeps the gauge directions far above rounding.
+    "i-dogleg": dict(shape=(150, 3000, 14000), seed=5, perturb=(1e-3, 1e-2, 1e-2), kmax=4, silent="middle", const_cams=(),
+                     options=dict(min_lm_diagonal=2.0 ** (12 - 1075), zero_columns_in_ieee_double=True),
+                     solves=(6, 2, 1, 2), mus=(1e-3, 2e-3, 4e-4, 8e-4)),
 }
+REFERENCE_ONLY_OPTIONS = ("zero_columns_in_ieee_double",)
 
 
 @functools.lru_cache(maxsize=None)
 def problem(name):
     c = CASES[name]
-    return bal.generate(*c["shape"], seed=c["seed"], perturb=c["perturb"])
+    prob = bal.generate(*c["shape"], seed=c["seed"], perturb=c["perturb"])
+    if c.get("silent"):
+        prob = silent_component(name)[0]
+    return prob
+
+
+@functools.lru_cache(maxsize=None)
+def silent_component(name):
+    """(the problem with the silent component appended, the columns of x that belong to the component)."""
+    import failure_cases as fc   # (imports this module: not at the top)
+    c = CASES[name]
+    prob, comp = fc._with_silent_component(bal.generate(*c["shape"], seed=c["seed"], perturb=c["perturb"]), c["silent"])
+    nc = 9 * prob.num_cameras
+    return prob, [9 * a + k for a in comp["cameras"] for k in range(9)] + [nc + 3 * q + k for q in comp["on_axis"] + comp["off_axis"] for k in range(3)]
 
 
 def masks(name):
     c, prob = CASES[name], problem(name)
     cam_mask = np.full(prob.num_cameras, 0b111000000 if c.get("subset") else 0, dtype=np.int32)
-    cam_mask[list(CONST_CAMS)] = 0x1ff
+    cam_mask[list(c.get("const_cams", CONST_CAMS))] = 0x1ff
     pt_mask = np.zeros(prob.num_points, dtype=np.int32)
     pt_mask[list(c.get("const_pts", ()))] = 7
     return cam_mask, pt_mask

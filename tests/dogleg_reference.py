@@ -221,6 +221,7 @@ def solve(model, cost, x0, options=None, dtype=np.float64, schur=None):
             break
         iteration += 1
         was_reused = reuse
+        solves, quotients = 0, []   # linear solves of this iteration; (mu, quotient, quotient / 2^-1075, zero columns) of each under the option
         if not reuse:
             diag = np.sqrt(np.clip(colsq, T(o["min_lm_diagonal"]), T(o["max_lm_diagonal"])))
             ghat = gs / diag
@@ -228,6 +229,19 @@ def solve(model, cost, x0, options=None, dtype=np.float64, schur=None):
             while mu < MAX_MU:
                 try:
                     D2 = T(mu) * diag * diag
+                    solves += 1
+                    if o.get("zero_columns_in_ieee_double"):
+                        # (case i-dogleg of tests/dogleg_cases.py: a column that is exactly zero, with a zero gradient entry, has
+                        # min_lm_diagonal / (1 / mu) on its diagonal, formed in IEEE double as the device forms it, in BOTH precisions — where
+                        # it underflows to 0 the system is not positive definite; where it is positive the unknown is 0 whatever the value, so
+                        # the solve proceeds with a unit diagonal there.  The same option of tests/failure_reference.py says more.)
+                        zero = (colsq == 0) & (gs == 0)
+                        with np.errstate(under="ignore"):
+                            quotient = float(np.float64(o["min_lm_diagonal"]) / (np.float64(1.0) / np.float64(mu)))
+                        quotients.append((mu, quotient, float(LD(o["min_lm_diagonal"]) * LD(mu) / LD(2) ** -1075), int(np.count_nonzero(zero))))
+                        if zero.any() and quotient == 0.0:
+                            raise NotPositiveDefinite()
+                        D2[zero] = 1
                     y = _gauss_newton_schur(lin, schur[0], schur[1], D2, gs, T) if schur else _gauss_newton_dense(lin, n, D2, gs, T)
                     break
                 except NotPositiveDefinite:
@@ -275,7 +289,7 @@ def solve(model, cost, x0, options=None, dtype=np.float64, schur=None):
             entry(valid=0, success=0)
             continue
         invalid = 0
-        extra = dict(branch=branch, reused=was_reused, dogleg_step_norm=float(dogleg_norm), model_cost_change=float(mcc),
+        extra = dict(solves=solves, quotients=quotients, branch=branch, reused=was_reused, dogleg_step_norm=float(dogleg_norm), model_cost_change=float(mcc),
                      w_r=float(st["wr"]), g_g=float(st["gg"]), scaled_step=np.asarray(scaled, dtype=T),
                      a=float(ab[0]), b=float(ab[1]), products=tuple(T(st[f]) for f in ("wr", "mr", "ww", "wm", "mm")), model_cost_change_ld=T(mcc))
         new_cost = cost(x_new)

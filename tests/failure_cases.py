@@ -22,6 +22,13 @@ bundle-adjustment problem whose one focal length is far off is dominated by the 
 compensate (|step| 40 .. 100 against a displacement of the focal coordinate of 5 .. 15), so no barrier on one coordinate can be
 overshot by a tenth of the whole step; the displacement along the barrier's normal is what decides the side a candidate lands on.
 
+Case i (linear solves that are not valid followed by valid ones, several times in one solve): its construction, and why its zero
+columns are points' and none of its coordinates is inert, stands above its cases.  Its decisions are those of a quotient that rounds
+to 0 or does not: exact wherever the radius was reached by powers of two and by x 3, and held 5 % away from 2^-1075 elsewhere
+(tests/test_failure_cpu.py).  margins() does not apply to kind i: it measures a candidate's distance from a barrier coordinate, and
+these cases have no barrier — no candidate fails; what stands in its place is the quotient's margin above and the margin of every
+deciding relative decrease from min_relative_decrease, asserted in the same CPU test.
+
 Dense rows and case f: dense_synth's rows are r_i = tanh(a_i . x / sqrt(n)) - y_i with |a_ij| < 3.5, so no Jacobian entry exceeds
 3.5 / sqrt(n): the overflow of J^T J cannot be produced, and dense rows have no case f."""
 import functools
@@ -35,8 +42,9 @@ from skeres_amd.examples.traced_functors import angle_axis_rotate_point
 
 import step_check as sc
 import failure_reference as fr
+import dogleg_reference as dr
 from dogleg_cases import TOL
-from helpers import curve_fitting_data
+from helpers import curve_fitting_data, sk_loss
 
 LD = np.longdouble
 # The radius sequence: 1e-14 relative wherever the reference's own radius is exact — the initial radius divided by powers of two (every
@@ -217,8 +225,8 @@ def _stiff_problem(n):
 
 
 @functools.lru_cache(maxsize=None)
-def _bal(shape=BAL_SHAPE, seed=BAL_SEED, perturb=(1e-4, 1e-3, 1e-3)):
-    return bal.generate(*shape, seed=seed, perturb=perturb)
+def _bal(shape=BAL_SHAPE, seed=BAL_SEED, perturb=(1e-4, 1e-3, 1e-3), revisits=()):
+    return bal.generate(*shape, seed=seed, perturb=perturb, revisits=list(revisits))
 
 
 def _bal_offsets(prob):
@@ -274,9 +282,9 @@ for _bad in ("nan", "inf"):
 _case("b-DENSE_QR", kind="b", backend="DENSE_QR", family="curve-host", reach={"initial-evaluation-failed"})
 _case("b-DENSE_SCHUR", kind="b", backend="DENSE_SCHUR", family="bal-host-first-call", reach={"initial-evaluation-failed"})
 # (One DENSE_SCHUR case, the replay option left on: a recorded functor, like a director block, switches the hipGraph replay of the
-# iteration off in BalSolver::setup whatever the option says, and the compiled Snavely functor has no barrier.  OPEN: no failed candidate and
-# no invalid solve runs inside a replayed graph, so the zeroing of the failure flag and of info inside the captured sequence, on either
-# parity, is not exercised by any test.)
+# iteration off in BalSolver::setup whatever the option says, and the compiled Snavely functor has no barrier.  Invalid solves inside a
+# replayed graph: case i-graph below.  OPEN: no failed CANDIDATE runs inside a replayed graph, so the zeroing of the failure flag after one,
+# inside the captured sequence, is not exercised by any test.)
 _case("c-DENSE_SCHUR", kind="c", backend="DENSE_SCHUR", family="log-focal", start=8.0, replay=True,
           reach={"candidate-failed", "accepted"}, barrier=(U, 0.0), failed_candidates=4, converges=True)
 _case("d-DENSE_QR", kind="d", backend="DENSE_QR", family="logfit", host=True, x0=(1.0, 5.0), options=dict(initial_trust_region_radius=10.0),
@@ -308,6 +316,99 @@ H_SHAPE, H_SEED = (150, 3000, 14000), 5
 for _plan, _knobs in (("retained", {"setRetainedPoints": ("on", 3)}), ("dissected", {"setCholeskyDissection": "on"})):
     _case("h-%s" % _plan, kind="h", backend="DENSE_SCHUR", family="log-focal", start=12.0, shape=H_SHAPE, seed=H_SEED, knobs=_knobs,
           options=dict(max_num_iterations=8), reach={"candidate-failed", "accepted"}, barrier=(U, 0.0), failed_candidates=4, reference_of="h-retained")
+
+
+# case i: linear solves that are not valid FOLLOWED by valid ones, several times, on every plan of the reduced system.  Only the
+# radius changes between an invalid solve and the next (x stays), so validity must hang on the radius alone, and without any rounding
+# that device and reference could do differently: a FREE column of the Jacobian that is exactly zero has the LM diagonal
+# min_lm_diagonal / radius, and with min_lm_diagonal = 2^-1075 R* (R* a power of two) that quotient rounds to 0 in IEEE double exactly
+# where radius >= R* — a zero pivot — and to a positive subnormal below.  Ceres does the same with such a column; no held coordinate
+# and no parameterization takes part.
+#   The zero column is a POINT's, never a camera's: bal_point_block_kernel factors its 3 x 3 block with sqrt and /, correctly rounded
+# down to the subnormals, where wave_potrf32 takes __builtin_amdgcn_rcp of the pivot, which overflows for a subnormal one — a camera
+# column with a subnormal diagonal is never valid on the device (open list).  So every camera column of these
+# problems is non-zero, and none of their coordinates is inert (held, padded or constant).
+#   The silent co-axial component (_with_silent_component): cameras A and B with zero angle-axis on the z axis, k1 = k2 = 0, focal
+# lengths 512 and 1024, A at the origin, B at t_z = -4.  ON_AXIS points are seen by A and B alone at observation (0, 0): their
+# z-column is exactly 0 (the derivative along the axis vanishes) and so are their residuals.  OFF_AXIS points are seen by A and B
+# alone too, with coordinates that make every operation of the projection exact, so their residuals are exactly 0 as well; they keep
+# the cameras' t_z, f, k1 and k2 columns non-zero.  The component's gradient is exactly 0: it never moves, the zero columns persist
+# through every accepted step, and the episodes recur whenever the radius has grown past R* again.  max_trust_region_radius = 2^16
+# keeps the component's gauge directions damped far above rounding.  ("once": the two cameras also see generic points, so they move
+# with the first accepted step and the one episode is that of iteration 1.)
+R_STAR = 2.0 ** 12
+I_MIN_LM_DIAGONAL = 2.0 ** (12 - 1075)
+I_OPTIONS = dict(min_lm_diagonal=I_MIN_LM_DIAGONAL, initial_trust_region_radius=4 * R_STAR, max_trust_region_radius=2.0 ** 16)
+ON_AXIS = np.array([[0.0, 0.0, -2.0], [0.0, 0.0, -4.0], [0.0, 0.0, -8.0]])
+OFF_AXIS = np.array([[1.0, 2.0, -4.0], [-2.0, 1.0, -4.0], [2.0, -1.0, -4.0], [-1.0, -3.0, -4.0], [3.0, 1.0, -4.0]])
+SILENT_CAMERAS = np.array([[0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 512.0, 0.0, 0.0], [0.0, 0.0, 0.0, 0.0, 0.0, -4.0, 1024.0, 0.0, 0.0]])
+
+
+def _with_silent_component(prob, place, generic=0):
+    """prob with the silent component appended: its two cameras in the middle of the camera list ("middle") or behind it ("end"), its
+    points behind the points.  generic > 0: that many of prob's points seen by exactly two cameras have those two observations moved
+    to A and B, as A and B project the point as it stands (the variant with one episode).  Returns (problem, dict(cameras, on_axis,
+    off_axis: indices in the new problem))."""
+    C, P = prob.num_cameras, prob.num_points
+    a = C // 2 if place == "middle" else C
+    cam = np.where(prob.camera_index >= a, prob.camera_index + 2, prob.camera_index).astype(np.int32)
+    pt, obs = prob.point_index.copy(), prob.observations.copy()
+    pts = np.concatenate([prob.points(), ON_AXIS, OFF_AXIS])
+    if generic:
+        count = np.bincount(prob.point_index, minlength=P)
+        moved = 0
+        for q in np.flatnonzero(count == 2):
+            # (a point of the slab in front of both cameras, near the axis)
+            o = np.flatnonzero(prob.point_index == q)
+            pts[q] = [0.25 * (moved + 1), -0.125 * (moved + 1), -6.0 - moved]
+            proj, depth = bal.snavely_project(SILENT_CAMERAS, np.stack([pts[q], pts[q]]))
+            assert (depth < 0).all()
+            cam[o] = [a, a + 1]
+            obs[o] = proj + 0.25 * np.array([[1.0, -1.0], [-1.0, 1.0]])
+            moved += 1
+            if moved == generic:
+                break
+        assert moved == generic
+    extra = np.concatenate([ON_AXIS, OFF_AXIS])
+    proj, depth = bal.snavely_project(np.repeat(SILENT_CAMERAS, len(extra), axis=0), np.tile(extra, (2, 1)))
+    assert (depth < 0).all()
+    cam = np.concatenate([cam, np.repeat([a, a + 1], len(extra)).astype(np.int32)])
+    pt = np.concatenate([pt, np.tile(P + np.arange(len(extra)), 2).astype(np.int32)])
+    obs = np.concatenate([obs, proj])
+    cams = np.concatenate([prob.cameras()[:a], SILENT_CAMERAS, prob.cameras()[a:]])
+    out = bal.BalProblem(C + 2, P + len(extra), cam, pt, np.ascontiguousarray(obs), np.concatenate([cams.ravel(), pts.ravel()]))
+    return out, dict(cameras=(a, a + 1), on_axis=tuple(range(P, P + len(ON_AXIS))), off_axis=tuple(range(P + len(ON_AXIS), P + len(extra))))
+
+
+I_SHAPE, I_SEED = H_SHAPE, H_SEED
+I_REACH = {"invalid-step", "accepted"}
+
+
+def _case_i(name, reference_of=None, **kw):
+    kw.setdefault("shape", I_SHAPE)
+    kw.setdefault("seed", I_SEED)
+    kw.setdefault("place", "middle")
+    kw.setdefault("perturb", (1e-2, 1e-1, 1e-1))
+    kw.setdefault("kmax", 9)
+    kw.setdefault("episodes", 3)
+    kw["options"] = dict(I_OPTIONS, max_num_iterations=kw["kmax"], **kw.get("options", {}))
+    _case(name, kind="i", backend="DENSE_SCHUR", family="silent", reach=I_REACH, reference_options=dict(zero_columns_in_ieee_double=True),
+          reference_of=reference_of or name, **kw)
+
+
+_case_i("i-resident", knobs={"setGraphReplay": False}, plan=dict(cholesky_columns_resident=("gt", 0)))
+_case_i("i-launch-by-launch", reference_of="i-resident", knobs={"setGraphReplay": False}, resident=False, plan=dict(cholesky_columns_resident=("eq", 0)))
+_case_i("i-dissected", reference_of="i-resident", knobs={"setCholeskyDissection": "on", "setGraphReplay": False}, plan=dict(dissected=("eq", 1)))
+_case_i("i-retained", reference_of="i-resident", knobs={"setRetainedPoints": ("on", 3), "setGraphReplay": False}, plan=dict(retained_points=("eq", 3)))
+_case_i("i-huber", loss=("huber", 1.0), knobs={"setGraphReplay": False}, plan=dict(cholesky_columns_resident=("gt", 0)))
+_case_i("i-graph", shape=(49, 7776, 31843), seed=49, place="end", replay=True, plan=dict(graph_replay=("eq", 1)))
+# (the revisiting shape of tests/test_gpu_step_check.py::test_border_of_loop_closure_cameras_steps, its knobs; kmax = 8 holds the three
+# episodes and the accepted step behind the last — the reference of this one takes 14 s in double and 75 s in long double)
+_case_i("i-border", shape=(600, 6000, 26000), seed=9, revisits=((60, 350, 12, 40), (200, 520, 12, 40)), kmax=8,
+        knobs={"setCholeskyBorder": "on", "setRetainedPoints": "off", "setGraphReplay": False}, plan=dict(border_cameras=("gt", 0), retained_points=("eq", 0)))
+# (once the two cameras have moved, the on-axis points' depth is a nearly undetermined direction and what follows the first accepted step
+# is rejected: one rejected step is kept, whose rho = -0.29 is far from any threshold and leaves the radius in the exact sequence)
+_case_i("i-once", shape=(6, 40, 110), seed=BAL_SEED, perturb=(1e-4, 1e-3, 1e-3), place="end", generic=4, episodes=1, kmax=4, knobs={"setGraphReplay": False})
 
 
 def names(kind=None, backend=None):
@@ -348,7 +449,24 @@ def _beyond(c, name):
 
 
 def _prob(c):
+    if c["family"] == "silent":
+        return _silent(c["shape"], c["seed"], c["perturb"], c["place"], c.get("generic", 0), c.get("revisits", ()))[0]
     return _bal(c.get("shape", BAL_SHAPE), c.get("seed", BAL_SEED))
+
+
+@functools.lru_cache(maxsize=None)
+def _silent(shape, seed, perturb, place, generic, revisits=()):
+    return _with_silent_component(_bal(shape, seed, perturb, revisits), place, generic)
+
+
+def component(name):
+    """Case i: the silent component of the case's problem — cameras, on_axis and off_axis points (indices), zero_columns (the
+    on-axis points' z coordinates in x) and columns (every coordinate of the component in x)."""
+    c = CASES[name]
+    prob, comp = _silent(c["shape"], c["seed"], c["perturb"], c["place"], c.get("generic", 0), c.get("revisits", ()))
+    nc = 9 * prob.num_cameras
+    cols = [9 * a + k for a in comp["cameras"] for k in range(9)] + [nc + 3 * q + k for q in comp["on_axis"] + comp["off_axis"] for k in range(3)]
+    return dict(comp, zero_columns=[nc + 3 * q + 2 for q in comp["on_axis"]], columns=cols)
 
 
 def start(name):
@@ -474,6 +592,8 @@ def _model(c):
         consts, _ = dense_synth.generate(100, 3, seed=3)
         return sc.DenseRowsModel(consts, 3)
     prob = _prob(c)
+    if fam == "silent":   # (the oracle's Jacobian in double, as the step check has it)
+        return sc.BalModel(prob, loss=c.get("loss"))
     offs, kind, n = _bal_offsets(prob), _bal_kind(prob), prob.num_parameters
     plain_cap = _log_focal_problem(prob, None)[1]
     if fam in ("bal", "bal-host-first-call", "bal-host-nan-jacobian"):
@@ -513,7 +633,10 @@ def reference(name, long_double=False):
     """The reference's run of a case; shared by the tests, not to be modified.  (The two plans of case h are one problem.)"""
     if CASES[name].get("reference_of", name) != name:
         return reference(CASES[name]["reference_of"], long_double)
-    return fr.solve(model(name), start(name), options(name), dtype=LD if long_double else np.float64, schur=schur(name))
+    c = CASES[name]
+    cost_of = dr.bal_cost(_prob(c), c["loss"]) if c["family"] == "silent" and c.get("loss") else None   # (1/2 sum rho, the oracle's residuals in double)
+    return fr.solve(model(name), start(name), dict(options(name), **c.get("reference_options", {})), dtype=LD if long_double else np.float64,
+                    schur=schur(name), cost_of=cost_of)
 
 
 def margins(name, run=None):
@@ -684,8 +807,10 @@ def device_problem(name):
     else:
         prob = _prob(c)
         offs = _bal_offsets(prob)
-        if fam == "bal":
-            problem.addResidualBlocks(sk.SnavelyReprojectionError.FUNCTOR_ID, prob.observations, trivial, params, offs)
+        if fam in ("bal", "silent"):
+            loss = sk_loss(c["loss"]) if c.get("loss") else trivial
+            keep.append(loss)
+            problem.addResidualBlocks(sk.SnavelyReprojectionError.FUNCTOR_ID, prob.observations, loss, params, offs)
         elif fam in ("log-focal", "abs-focal", "sqrt-focal", "stiff-snavely"):
             if fam == "stiff-snavely":
                 tape, _, cap, _, _ = _stiff_snavely_group(prob)
@@ -729,13 +854,15 @@ def device_problem(name):
     return problem, params, len(x0), keep
 
 
-def device_options(name):
+def device_options(name, override=None):
+    """The case's options on the device; override: option values that replace the case's (the fresh-start twin of case i)."""
     c = CASES[name]
     o = sk.Solver.Options()
     o.setLinearSolverType(sk.LinearSolverType.DENSE_NORMAL_CHOLESKY if c["backend"] == "ROWS" else getattr(sk.LinearSolverType, c["backend"]))
     setters = dict(initial_trust_region_radius="setInitialTrustRegionRadius", jacobi_scaling="setJacobiScaling", max_num_iterations="setMaxNumIterations",
-                   max_num_consecutive_invalid_steps="setMaxNumConsecutiveInvalidSteps")
-    for k, v in options(name).items():
+                   max_num_consecutive_invalid_steps="setMaxNumConsecutiveInvalidSteps", min_lm_diagonal="setMinLmDiagonal",
+                   max_trust_region_radius="setMaxTrustRegionRadius")
+    for k, v in dict(options(name), **(override or {})).items():
         getattr(o, setters[k])(v)
     if "replay" in c:
         o.setGraphReplay(c["replay"])
@@ -746,11 +873,12 @@ def device_options(name):
     return o
 
 
-def device_run(name, stats=()):
+def device_run(name, stats=(), override=None, built=None, end_stats=()):
     """Steps a StepSolver over the case to its end; the run in the reference's shape, plus xs (x after create and after every
-    step) and the named stats read after create."""
-    problem, params, n, keep = device_problem(name)
-    solver = sk.StepSolver(device_options(name), problem)
+    step), the named stats read after create and (end_stats) those read after the last step.  built: device_problem's tuple, where
+    the caller has made it."""
+    problem, params, n, keep = device_problem(name) if built is None else built
+    solver = sk.StepSolver(device_options(name, override), problem)
     st = {nm: solver.stat(nm) for nm in stats}
     summary = sk.Solver.Summary()
     solver.finish(summary)
@@ -764,4 +892,4 @@ def device_run(name, stats=()):
     solver.finish(summary)
     return dict(x=params.toArray(n), xs=xs, log=summary.iterations(), termination=TERMINATION[summary.terminationType()], message=summary.message(),
                 num_successful_steps=summary.numSuccessfulSteps(), num_unsuccessful_steps=summary.numUnsuccessfulSteps(),
-                final_cost=summary.finalCost(), stats=st, report=summary.fullReport())
+                final_cost=summary.finalCost(), stats=st, end_stats={nm: solver.stat(nm) for nm in end_stats}, report=summary.fullReport())

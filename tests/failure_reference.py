@@ -14,6 +14,15 @@ linear algebra tests/dogleg_reference.py shares; neither the oracle nor anything
     evaluation after an        FAILURE "Residual and Jacobian evaluation failed.", the iteration NOT logged and not counted as
     accepted step fails        successful, x the accepted candidate, the final cost not pinned (lm.cpp leaves what evaluate() wrote)
 
+Option zero_columns_in_ieee_double (case i of tests/failure_cases.py only; absent, nothing changes): a column of the scaled Jacobian
+that is exactly zero, with a zero gradient entry, has min_lm_diagonal / radius on its diagonal and nothing else in its row.  That
+quotient is formed in IEEE double in BOTH precisions of the reference — where it underflows to 0 the system is not positive definite
+and the solve is not valid; long double would not underflow there, and the underflow is what the case is about — and where it is
+positive the unknown is 0 whatever the value (the row is decoupled and its right-hand side is 0), so the solve proceeds with a unit
+diagonal there: a subnormal pivot never enters the reference's own arithmetic.  Each entry then carries radius_used,
+radius_used_exact, zero_columns, zero_quotient and zero_quotient_over_half_ulp (the exact quotient over 2^-1075).  cost_of: the cost
+where a robust loss makes it something else than 1/2 sum of the squared corrected residuals.
+
 solve() returns a dict: x, log (the device's fields per logged iteration plus model_cost_change, candidate (the point tried),
 candidate_failed, radius_exact (no update of the radius so far went through rho: see failure_cases.compare)), termination, message, num_successful_steps, num_unsuccessful_steps, final_cost (None: not pinned), reached (the
 set of branches the run went through: the names of BRANCHES)."""
@@ -61,8 +70,10 @@ class CallableModel(sc._Model):
                    [(np.asarray(J[q], dtype=LD)[None, :, :], np.array([offs[q]], dtype=np.int64)) for q in range(len(offs))])
 
 
-def _evaluate(model, x, s, T, jac):
-    """(cost, lin) at x with the columns scaled by s, or None where the evaluation fails (the module's docstring)."""
+def _evaluate(model, x, s, T, jac, cost_of=None):
+    """(cost, lin) at x with the columns scaled by s, or None where the evaluation fails (the module's docstring).  cost_of: x -> the
+    cost, where 1/2 sum r^2 of the model's residuals is not it (a robust loss: the model's residuals are the corrected ones, whose
+    squares sum to something else than sum rho(|r|^2))."""
     if hasattr(model, "failed") and model.failed(x, jac):
         return None
     with np.errstate(all="ignore"):
@@ -70,11 +81,22 @@ def _evaluate(model, x, s, T, jac):
         for r, terms in lin:
             if not np.all(np.isfinite(r)) or (jac and not all(np.all(np.isfinite(J)) for J, _ in terms)):
                 return None
-        cost = float(sum(np.sum(r * r) for r, _ in lin) / 2)
+        cost = float(sum(np.sum(r * r) for r, _ in lin) / 2) if cost_of is None else float(cost_of(x))
     return (cost, lin) if np.isfinite(cost) else None
 
 
-def solve(model, x0, options=None, dtype=np.float64, schur=None):
+def _zero_column_quotient(colsq, gs, min_lm_diagonal, radius):
+    """The columns of the scaled Jacobian that are exactly zero (with them their gradient entries), min_lm_diagonal / radius formed in
+    IEEE double whatever the precision of the run — where it underflows to 0 the pivot of such a column is 0 and the system is not
+    positive definite: that underflow is what case i is about, and long double has none there — and the exact quotient in units of
+    2^-1075, half the smallest subnormal double: it rounds to 0 (ties to even) exactly where that figure is <= 1."""
+    zero = (colsq == 0) & (gs == 0)
+    with np.errstate(under="ignore"):
+        quotient = float(np.float64(min_lm_diagonal) / np.float64(radius))
+    return zero, quotient, float(LD(min_lm_diagonal) / LD(radius) / LD(2) ** -1075)
+
+
+def solve(model, x0, options=None, dtype=np.float64, schur=None, cost_of=None):
     T = LD if dtype is LD else np.float64
     o = dict(DEFAULTS)
     o.update(options or {})
@@ -87,7 +109,7 @@ def solve(model, x0, options=None, dtype=np.float64, schur=None):
         out["reached"] = frozenset(out["reached"])
         return out
 
-    ev = _evaluate(model, x, np.ones(n, dtype=T), T, True)
+    ev = _evaluate(model, x, np.ones(n, dtype=T), T, True, cost_of)
     if ev is None:
         out["reached"].add("initial-evaluation-failed")
         return done(FAILURE, MSG_INITIAL, x, None)
@@ -95,7 +117,7 @@ def solve(model, x0, options=None, dtype=np.float64, schur=None):
     s = np.ones(n, dtype=T)
     if o["jacobi_scaling"]:
         s = (1 / (1 + np.sqrt(dr._colsq_and_gradient(lin, n, T)[0]))).astype(T)
-        c, lin = _evaluate(model, x, s, T, True)
+        c, lin = _evaluate(model, x, s, T, True, cost_of)
 
     def reductions(lin, x):
         with np.errstate(all="ignore"):
@@ -126,7 +148,16 @@ def solve(model, x0, options=None, dtype=np.float64, schur=None):
         ok = True
         with np.errstate(all="ignore"):
             D2 = np.clip(colsq, T(o["min_lm_diagonal"]), T(o["max_lm_diagonal"])) / radius
+            zero_ok, info = True, {}
+            if o.get("zero_columns_in_ieee_double"):
+                zero, quotient, ratio = _zero_column_quotient(colsq, gs, o["min_lm_diagonal"], radius)
+                info = dict(radius_used=float(radius), radius_used_exact=radius_exact, zero_columns=int(np.count_nonzero(zero)),
+                                   zero_quotient=quotient, zero_quotient_over_half_ulp=ratio)
+                zero_ok = not zero.any() or quotient > 0.0
+                D2[zero] = 1   # (a decoupled unknown with right-hand side 0: y_j = 0 under any positive diagonal)
             try:
+                if not zero_ok:
+                    raise dr.NotPositiveDefinite()
                 y = dr._gauss_newton_schur(lin, schur[0], schur[1], D2, gs, T) if schur else dr._gauss_newton_dense(lin, n, D2, gs, T)
                 ok = bool(np.all(np.isfinite(y)))
             except (dr.NotPositiveDefinite, np.linalg.LinAlgError):
@@ -140,18 +171,18 @@ def solve(model, x0, options=None, dtype=np.float64, schur=None):
             invalid += 1
             out["reached"].add("invalid-step")
             if invalid >= o["max_num_consecutive_invalid_steps"]:
-                entry(valid=0, success=0)
+                entry(valid=0, success=0, **info)
                 out["reached"].add("too-many-invalid-steps")
                 return done(FAILURE, MSG_INVALID % o["max_num_consecutive_invalid_steps"], x, c)
             radius = radius / T(decrease_factor)
             decrease_factor *= 2.0
-            entry(valid=0, success=0)
+            entry(valid=0, success=0, **info)
             continue
         invalid = 0
         x_new = (x.astype(T) + step * s).astype(np.float64)
-        cand = _evaluate(model, x_new, s, T, False)
+        cand = _evaluate(model, x_new, s, T, False, cost_of)
         new_cost = DBL_MAX if cand is None else cand[0]
-        extra = dict(model_cost_change=float(mcc), candidate=x_new, candidate_failed=cand is None, previous=x)
+        extra = dict(info, model_cost_change=float(mcc), candidate=x_new, candidate_failed=cand is None, previous=x)
         if cand is None:
             out["reached"].add("candidate-failed")
         cost_change = c - new_cost
@@ -164,7 +195,7 @@ def solve(model, x0, options=None, dtype=np.float64, schur=None):
             return done(CONVERGENCE, "Function tolerance reached. |cost_change|/cost: %e <= %e" % (abs(cost_change) / c, o["function_tolerance"]), x, c)
         rho = cost_change / float(mcc)
         if rho > o["min_relative_decrease"]:
-            ev = _evaluate(model, x_new, s, T, True)
+            ev = _evaluate(model, x_new, s, T, True, cost_of)
             if ev is None:
                 out["reached"].add("evaluation-after-accept-failed")
                 return done(FAILURE, MSG_EVALUATION, x_new, None)

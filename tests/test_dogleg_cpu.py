@@ -119,3 +119,24 @@ def test_powell_reaches_its_minimum(built):
         x, log = dr.solve(model, dr.blocks_cost(model), x0, dict(max_num_iterations=200, function_tolerance=0.0, parameter_tolerance=0.0,
                                                                   gradient_tolerance=1e-30), dtype=dtype)
         assert log[-1]["cost"] < 1e-20, log[-1]["cost"]
+
+
+def test_i_dogleg_reaches_the_mu_loop(built):
+    """No other case of tests/dogleg_cases.py takes a second turn of `mu *= 10 while the damped system is not positive definite`
+    (asserted here); i-dogleg takes five at iteration 1 and one each at iterations 2 and 4, in double and in long double alike, every
+    decision of the quotient at least 15 % from 2^-1075, the silent component's columns exactly zero and its gradient exactly zero."""
+    for other in sorted(set(dc.CASES) - {"i-dogleg"}):
+        assert all(e.get("solves", 1) <= 1 for e in dc.reference(other)[1]), other
+    c = dc.CASES["i-dogleg"]
+    prob, cols = dc.silent_component("i-dogleg")
+    for long_double in (False, True):
+        x, log = dc.reference("i-dogleg", long_double)
+        assert [e["solves"] for e in log[1:]] == list(c["solves"])
+        for e, mu in zip(log[1:], c["mus"]):
+            assert e["step_is_valid"] and e["step_is_successful"] and not e["reused"]
+            *failed, held = e["quotients"]
+            assert held[0] == pytest.approx(mu, rel=1e-12) and held[1] > 0.0 and held[2] >= 1.15 and held[3] == 3
+            for _, quotient, over_half_ulp, zero_columns in failed:
+                assert quotient == 0.0 and over_half_ulp <= 0.85 and zero_columns == 3
+        assert np.array_equal(x[cols].view(np.uint64), prob.parameters[cols].view(np.uint64))   # the component never moves
+    assert dc.model("i-dogleg").free.all()   # no inert coordinate

@@ -175,6 +175,169 @@ def test_planted_defect_in_the_log_is_rejected(defect):
         fc.compare(run, ref, fc.start(name))
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# case i: invalid linear solves followed by valid ones (the silent co-axial component of tests/failure_cases.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+I_REFERENCED = [n for n in fc.names(kind="i") if fc.CASES[n]["reference_of"] == n]
+QUOTIENT_MARGIN = 0.05   # how far min_lm_diagonal / radius stays from 2^-1075 wherever the radius carries a rounding
+
+
+def episodes(log):
+    """[(first, last)] of the runs of consecutive invalid entries of a log."""
+    out, k = [], 1
+    while k < len(log):
+        if not log[k]["step_is_valid"]:
+            first = k
+            while k + 1 < len(log) and not log[k + 1]["step_is_valid"]:
+                k += 1
+            out.append((first, k))
+        k += 1
+    return out
+
+
+@pytest.mark.parametrize("name", I_REFERENCED)
+def test_i_the_silent_component_is_what_the_case_says(name):
+    """The oracle's Jacobian at x0: the on-axis points' z columns, and no others, are exactly zero (so no camera column is), and
+    the residuals of the component's own points are exactly zero, with them (where the component has no generic point) its gradient."""
+    c, comp = fc.CASES[name], fc.component(name)
+    prob, x0 = fc._prob(c), fc.start(name)
+    n = prob.num_parameters
+    colsq, grad = np.zeros(n, dtype=fc.LD), np.zeros(n, dtype=fc.LD)
+    own = np.isin(prob.point_index, comp["on_axis"] + comp["off_axis"])
+    assert own.sum() == 2 * len(comp["on_axis"] + comp["off_axis"]) and set(prob.camera_index[own]) == set(comp["cameras"])
+    at = 0
+    for r, terms in fc.model(name).chunks(x0):
+        assert not np.any(r[own[at:at + len(r)]])   # exactly zero, whatever the loss
+        at += len(r)
+        for J, first in terms:
+            for b in range(J.shape[0]):
+                colsq[first[b]:first[b] + J.shape[2]] += np.sum(J[b] * J[b], axis=0)
+                grad[first[b]:first[b] + J.shape[2]] += J[b].T @ r[b]
+    assert sorted(np.flatnonzero(colsq == 0).tolist()) == sorted(comp["zero_columns"])
+    assert np.all(colsq[:9 * prob.num_cameras] > 0)
+    if not c.get("generic"):
+        assert not np.any(grad[comp["columns"]])
+        assert not np.any(np.isin(prob.camera_index[~own], comp["cameras"]))
+
+
+@pytest.mark.parametrize("name", I_REFERENCED)
+def test_i_every_decision_of_the_quotient_is_exact_or_far(name):
+    c = fc.CASES[name]
+    comp = fc.component(name)
+    for long_double in (False, True):
+        run = fc.reference(name, long_double)
+        log = run["log"]
+        print(name, "long double" if long_double else "double",
+              [(k, e["radius_used"] / fc.R_STAR, e["radius_used_exact"], round(e["zero_quotient_over_half_ulp"], 4), e["zero_columns"]) for k, e in enumerate(log) if k], flush=True)
+        for k, e in enumerate(log[1:], 1):
+            underflows = e["zero_quotient"] == 0.0
+            assert underflows == (e["zero_quotient_over_half_ulp"] <= 1.0)   # (ties to even: 2^-1075 itself rounds to 0)
+            if e["radius_used_exact"]:   # a radius reached by powers of two and by x 3: the same bits on the device, the decision exact
+                assert e["radius_used"] == log[k - 1]["trust_region_radius"] and log[k - 1]["radius_exact"]
+            else:
+                assert abs(e["zero_quotient_over_half_ulp"] - 1.0) >= QUOTIENT_MARGIN, (k, e["zero_quotient_over_half_ulp"])
+            # the quotient alone decides: no solve of these cases is invalid for another reason
+            assert bool(e["step_is_valid"]) == (not (e["zero_columns"] and underflows)), k
+            if e["step_is_valid"] and e["relative_decrease"] != 0.0:
+                assert abs(e["relative_decrease"] - 1e-3) >= RHO_MARGIN, (k, e["relative_decrease"])
+        ep = episodes(log)
+        assert len(ep) >= c["episodes"] and (c["episodes"] != 1 or (len(ep) == 1 and ep[0][0] == 1)), ep
+        assert ep[0][0] == 1 and ep[0][1] >= 2   # at least two invalid solves at iteration 1
+        for first, last in ep:
+            assert last + 1 < len(log) and log[last + 1]["step_is_valid"] and log[last + 1]["step_is_successful"], (first, last)
+        if c["episodes"] > 1:
+            accepted_before = [sum(int(e["step_is_successful"]) for e in log[1:first]) for first, _ in ep]
+            assert {a % 2 for a in accepted_before} == {0, 1}, accepted_before   # both parities of the replayed graph
+            assert log[1]["zero_columns"] == log[-1]["zero_columns"] == len(comp["zero_columns"])   # the zero columns persist
+            x = run["x"]
+            assert np.array_equal(fc.bits(x[comp["columns"]]), fc.bits(fc.start(name)[comp["columns"]]))   # the component never moves
+        else:
+            assert log[-1]["zero_columns"] == 0   # its cameras moved with the first accepted step
+
+
+def _invalid_moved_by_an_ulp(run):
+    k = next(k for k, e in enumerate(run["log"]) if not e["step_is_valid"])
+    run["xs"][k] = run["xs"][k].copy()
+    run["xs"][k][7] = np.nextafter(run["xs"][k][7], np.inf)
+
+
+def _invalid_entry_missing(run):
+    k = next(k for k, e in enumerate(run["log"]) if not e["step_is_valid"])
+    del run["log"][k]
+    del run["xs"][k]
+
+
+@pytest.mark.parametrize("defect", ["an invalid iteration that moved x by one ulp", "a log with one invalid entry missing"])
+def test_i_planted_defect_in_the_log_is_rejected(defect):
+    name = "i-once"
+    ref = fc.reference(name)
+    run = _as_device(ref, name)
+    fc.compare(run, ref, fc.start(name))
+    (_invalid_moved_by_an_ulp if "ulp" in defect else _invalid_entry_missing)(run)
+    with pytest.raises(AssertionError):
+        fc.compare(run, ref, fc.start(name))
+
+
+def _recovery_step(name, radius, stale=None):
+    """The step of case `name` from x0 at `radius` through the Schur complement of the dense normal equations, in double: x0 - s y.
+    stale: (camera a, camera b, 9 x 9 block) added to S[a, b] and its transpose to S[b, a] before the reduced solve."""
+    import step_check as sc
+    c = fc.CASES[name]
+    prob, x0, model = fc._prob(c), fc.start(name), fc.model(name)
+    n, nc = prob.num_parameters, 9 * prob.num_cameras
+    s = np.asarray(sc.jacobi_scale(model, x0), dtype=np.float64)
+    rows = []
+    res = []
+    for r, terms in model.chunks(x0):
+        for b in range(r.shape[0]):
+            row = np.zeros((r.shape[1], n))
+            for J, first in terms:
+                row[:, first[b]:first[b] + J.shape[2]] = np.asarray(J[b], dtype=np.float64)
+            rows.append(row * s)
+            res.append(np.asarray(r[b], dtype=np.float64))
+    J, r = np.concatenate(rows), np.concatenate(res)
+    colsq = np.sum(J * J, axis=0)
+    D2 = np.clip(colsq, c["options"]["min_lm_diagonal"], 1e32) / radius
+    D2[colsq == 0] = 1.0   # (y_j = 0 under any positive diagonal)
+    A, g = J.T @ J + np.diag(D2), J.T @ r
+    App_inv = np.linalg.inv(A[nc:, nc:])
+    S = A[:nc, :nc] - A[:nc, nc:] @ App_inv @ A[nc:, :nc]
+    if stale is not None:
+        a, b, block = stale
+        S[9 * a:9 * a + 9, 9 * b:9 * b + 9] += block
+        S[9 * b:9 * b + 9, 9 * a:9 * a + 9] += block.T
+    yc = np.linalg.solve(S, g[:nc] - A[:nc, nc:] @ App_inv @ g[nc:])
+    yp = App_inv @ (g[nc:] - A[nc:, :nc] @ yc)
+    return x0 - s * np.concatenate([yc, yp]), S
+
+
+@pytest.mark.parametrize("defect", ["none", "the previous radius's diagonal", "a stale block in S"])
+def test_i_planted_defect_in_the_recovery_step_is_rejected(defect):
+    """The step check that tests/test_gpu_failure.py holds the first valid step after an episode to: it passes a step computed
+    from the system of the recovery radius, and rejects one computed with the diagonal of the radius before (the last invalid
+    solve's) or from an S in which a block that should be zero kept an earlier assembly's entries."""
+    import step_check as sc
+    name = "i-once"
+    ref, x0 = fc.reference(name), fc.start(name)
+    k = episodes(ref["log"])[0][1] + 1
+    radius, previous = ref["log"][k - 1]["trust_region_radius"], ref["log"][k - 2]["trust_region_radius"]
+    assert previous == 4 * radius
+    stale = None
+    if defect.startswith("a stale"):
+        _, S = _recovery_step(name, radius)
+        comp = fc.component(name)
+        a, b = 0, comp["cameras"][0]   # two cameras that share no point: their block of S is zero
+        assert not np.any(S[9 * a:9 * a + 9, 9 * b:9 * b + 9])
+        stale = (a, b, S[9:18, 0:9].copy())   # what the block of cameras (1, 0) holds
+    x1, _ = _recovery_step(name, previous if defect.startswith("the previous") else radius, stale)
+    kw = dict(min_lm_diagonal=fc.CASES[name]["options"]["min_lm_diagonal"])
+    if defect == "none":
+        print(sc.check(fc.model(name), x0, x0, x1, ref["log"], k, **kw))
+        return
+    with pytest.raises(AssertionError):
+        sc.check(fc.model(name), x0, x0, x1, ref["log"], k, **kw)
+
+
 def test_nan_dropped_from_the_gradient_norm_is_rejected():
     """What a device that reduces max |g| with fmax makes of case g: the evaluation passes for finite, the NaN reaches the
     factorisation, five invalid steps, FAILURE.  The invariants hold; the comparison still rejects the run."""

@@ -179,3 +179,25 @@ def test_a_nan_below_the_diagonal_is_reported():
         assert cc.solve_row_ratio(case.A, x, b, case.m) <= 1.0
         with pytest.raises(sk.SkeresError):
             sk.api.cholesky_solve(bad, b, **kw)
+
+
+FAILURE_COMBINATIONS = ([("automatic",) + cid for cid in cc.PLAN_CASES + cc.BORDERED_CASES] + [("pairs",) + cid for cid in cc.PLAN_CASES]
+                        + [(plan, "plan", shape) for plan in ("dissected", "segments") for shape in ("band", "two-wide-parts")])
+
+
+@pytest.mark.parametrize("plan,kind,shape", FAILURE_COMBINATIONS, ids=lambda v: str(v))
+def test_a_failed_factorisation_and_the_solve_after_it(plan, kind, shape):
+    """The automatic plan (resident panel chain, resident back-substitution), resident pairs, the two-way and the multi-way dissection
+    on the shapes their backward-error tests use: the good matrix, then a matrix with one negative eigenvalue in a middle block, then
+    the good matrix again; then one with a NaN below the diagonal, then the good matrix again (tests/chol_failure_worker.py, a
+    process per combination).  Both bad matrices must be reported as not positive definite — not as a time-out of the chain, which is
+    what a waiter that the failed block column did not release would end in — and the good matrix must give the same bits each time."""
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "chol_failure_worker.py")
+    env = dict(os.environ, SK_CHAIN_PAIR_MAX_TRAILING="56") if plan == "pairs" else {k: v for k, v in os.environ.items() if k != "SK_CHAIN_PAIR_MAX_TRAILING"}
+    out = subprocess.run([sys.executable, worker, plan, kind, shape], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    got = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("CHOL_FAILURE ")][-1][len("CHOL_FAILURE "):])
+    print(got)
+    assert "timed out" not in out.stderr, out.stderr[-2000:]
+    for message in got["messages"]:
+        assert message is not None and "not positive definite" in message and "timed out" not in message, got

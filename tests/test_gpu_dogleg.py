@@ -50,6 +50,7 @@ def _build(prob, loss=None, subset=False, const_cams=dc.CONST_CAMS, const_pts=()
 
 
 def _options(kmax, dogleg=True, knobs=None, **opt):
+    assert set(opt) <= {"initial_trust_region_radius", "jacobi_scaling"}, opt   # (anything else goes through knobs)
     o = sk.Solver.Options()
     o.setLinearSolverType(sk.LinearSolverType.DENSE_SCHUR)
     if dogleg:
@@ -366,3 +367,41 @@ def test_refusals():
     summary = sk.Solver.Summary()
     sk.ceres.solve(_options(3, dogleg=False), host, summary)
     assert summary.finalCost() < summary.initialCost()
+
+
+def test_mu_loop_after_factorisations_that_fail(tmp_path):
+    """Case i-dogleg (tests/dogleg_cases.py): the damped system is not positive definite at the first mu of iterations 1, 2 and 4 — a
+    zero pivot in a point block, NaN rows of S, info raised, the resident chain and back-substitution running on NaN — and the loop
+    factors again at ten times mu, up to five times, inside the same iteration.  The log to the reference; the number of linear solves
+    of every iteration and mu after it as the reference has them (a retry after a time-out of the chain would count as a solve more);
+    every iteration valid; the silent component by its bits.  The device run is tests/dogleg_worker.py's, in a process of its own."""
+    import os
+    import pickle
+    import subprocess
+    import sys
+    import failure_cases as fc
+    name = "i-dogleg"
+    c, prob = dc.CASES[name], dc.problem(name)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = str(tmp_path / "run.pickle")
+    out = subprocess.run([sys.executable, os.path.join(root, "tests", "dogleg_worker.py"), name, path], cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "DOGLEG_WORKER_OK" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
+    assert "timed out" not in out.stderr, out.stderr[-3000:]
+    with open(path, "rb") as f:
+        run = pickle.load(f)
+    ref = dc.reference(name)[1]
+    _against_reference(name, run)
+    assert run["plan"]["cholesky_columns_resident"] > 0
+    stats = run["stats"] + [run["final"]] * (c["kmax"] + 1 - len(run["stats"]))
+    solves = [int(stats[k]["linear_solves"] - stats[k - 1]["linear_solves"]) for k in range(1, c["kmax"] + 1)]
+    print(name, "linear solves per iteration", solves, "mu", [stats[k]["dogleg_mu"] for k in range(c["kmax"] + 1)], flush=True)
+    assert solves == [e["solves"] for e in ref[1:]] == list(c["solves"])
+    for k in range(1, c["kmax"] + 1):
+        assert run["log"][k]["step_is_valid"] and run["log"][k]["step_is_successful"], k
+        assert stats[k]["dogleg_mu"] == pytest.approx(ref[k]["mu"], rel=1e-12), k
+    # the component never moves (its gradient is exactly zero), whatever ran on NaN before the factorisation that held
+    cols = dc.silent_component(name)[1]
+    assert len(run["xs"]) >= c["kmax"]
+    for x in run["xs"][1:]:
+        assert np.array_equal(fc.bits(x[cols]), fc.bits(prob.parameters[cols]))
+        assert not np.array_equal(x, prob.parameters)
