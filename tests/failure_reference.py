@@ -96,8 +96,13 @@ def _zero_column_quotient(colsq, gs, min_lm_diagonal, radius):
     return zero, quotient, float(LD(min_lm_diagonal) / LD(radius) / LD(2) ** -1075)
 
 
-def solve(model, x0, options=None, dtype=np.float64, schur=None, cost_of=None):
+def solve(model, x0, options=None, dtype=np.float64, schur=None, cost_of=None, defect=None):
+    """defect (tests/test_termination_cpu.py: what the termination brackets must reject; absent, nothing changes): a dict of
+    xnorm (x -> the norm the parameter test uses instead of |x|), gradient_strict (< in the gradient test), radius_not_strict (<= in
+    the radius test), function_first (the function test before the parameter test), after_acceptance (a tolerance exit returns the
+    candidate), no_exit_entry (a tolerance exit logs nothing), exit_entry_successful (its entry is marked successful)."""
     T = LD if dtype is LD else np.float64
+    defect = defect or {}
     o = dict(DEFAULTS)
     o.update(options or {})
     n = model.n
@@ -122,7 +127,8 @@ def solve(model, x0, options=None, dtype=np.float64, schur=None, cost_of=None):
     def reductions(lin, x):
         with np.errstate(all="ignore"):
             colsq, gs = dr._colsq_and_gradient(lin, n, T)
-        return colsq, gs, float(np.max(np.abs(gs / s))), float(np.sqrt(np.sum(x.astype(T) ** 2)))
+        xnorm = float(defect["xnorm"](x)) if "xnorm" in defect else float(np.sqrt(np.sum(x.astype(T) ** 2)))
+        return colsq, gs, float(np.max(np.abs(gs / s))), xnorm
 
     colsq, gs, gmax, xnorm = reductions(lin, x)
     radius = T(o["initial_trust_region_radius"])
@@ -140,9 +146,9 @@ def solve(model, x0, options=None, dtype=np.float64, schur=None, cost_of=None):
     while True:
         if iteration >= o["max_num_iterations"]:
             return done(NO_CONVERGENCE, "Maximum number of iterations reached. Number of iterations: %d." % iteration, x, c)
-        if gmax <= o["gradient_tolerance"]:
+        if gmax < o["gradient_tolerance"] if defect.get("gradient_strict") else gmax <= o["gradient_tolerance"]:
             return done(CONVERGENCE, "Gradient tolerance reached. Gradient max norm: %e <= %e" % (gmax, o["gradient_tolerance"]), x, c)
-        if radius < o["min_trust_region_radius"]:
+        if radius <= o["min_trust_region_radius"] if defect.get("radius_not_strict") else radius < o["min_trust_region_radius"]:
             return done(CONVERGENCE, "Minimum trust region radius reached. Trust region radius: %e <= %e" % (radius, o["min_trust_region_radius"]), x, c)
         iteration += 1
         ok = True
@@ -187,12 +193,17 @@ def solve(model, x0, options=None, dtype=np.float64, schur=None, cost_of=None):
             out["reached"].add("candidate-failed")
         cost_change = c - new_cost
         step_norm = float(np.sqrt(np.sum((x.astype(T) - x_new.astype(T)) ** 2)))
-        if step_norm <= o["parameter_tolerance"] * (xnorm + o["parameter_tolerance"]):
-            entry(cost_change, step_norm, 0.0, 1, 0, **extra)
-            return done(CONVERGENCE, "Parameter tolerance reached. Relative step_norm: %e <= %e." % (step_norm / (xnorm + o["parameter_tolerance"]), o["parameter_tolerance"]), x, c)
-        if abs(cost_change) <= o["function_tolerance"] * c:
-            entry(cost_change, step_norm, 0.0, 1, 0, **extra)
-            return done(CONVERGENCE, "Function tolerance reached. |cost_change|/cost: %e <= %e" % (abs(cost_change) / c, o["function_tolerance"]), x, c)
+        def tolerance_exit(message):
+            if not defect.get("no_exit_entry"):
+                entry(cost_change, step_norm, 0.0, 1, 1 if defect.get("exit_entry_successful") else 0, **extra)
+            return done(CONVERGENCE, message, x_new if defect.get("after_acceptance") else x, c)
+
+        by_parameter = step_norm <= o["parameter_tolerance"] * (xnorm + o["parameter_tolerance"])
+        by_function = abs(cost_change) <= o["function_tolerance"] * c
+        if by_parameter and not (defect.get("function_first") and by_function):
+            return tolerance_exit("Parameter tolerance reached. Relative step_norm: %e <= %e." % (step_norm / (xnorm + o["parameter_tolerance"]), o["parameter_tolerance"]))
+        if by_function:
+            return tolerance_exit("Function tolerance reached. |cost_change|/cost: %e <= %e" % (abs(cost_change) / c, o["function_tolerance"]))
         rho = cost_change / float(mcc)
         if rho > o["min_relative_decrease"]:
             ev = _evaluate(model, x_new, s, T, True, cost_of)
