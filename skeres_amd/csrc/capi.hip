@@ -5,6 +5,7 @@
 #include <new>
 
 #include "bal_kernels.hpp"
+#include "chol_solve.hpp"
 #include "dense_kernels.hpp"
 #include "dense_rows_kernels.hpp"
 #include "evaluate_kernels.hpp"
@@ -1157,287 +1158,32 @@ int sk_synth_dense_targets(double seed, int m, int n, const double* x_star, doub
   SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
 
+// The Cholesky plans on a matrix given as such: argument checks here, the fronts in chol_fronts.cpp, the device in chol_solve.hip.
 int sk_cholesky_solve(int n, const double* A, const double* b, double* x, double* L, int group) {
   return sk_cholesky_solve_ex(n, A, b, x, L, group, nullptr, 0);
 }
-
-static int cholesky_solve_impl(int n, const double* A, const double* b, double* x, double* L, int group, const int* last, int automatic_plan, int border_begin_row);
 int sk_cholesky_solve_ex(int n, const double* A, const double* b, double* x, double* L, int group, const int* last, int automatic_plan) {
-  return cholesky_solve_impl(n, A, b, x, L, group, last, automatic_plan, -1);
-}
-int sk_cholesky_solve_bordered(int n, const double* A, const double* b, double* x, double* L, int group, int border_begin_row, int automatic_plan) {
-  if (border_begin_row < 0 || border_begin_row > n) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
-  return cholesky_solve_impl(n, A, b, x, L, group, nullptr, automatic_plan, border_begin_row);
-}
-static std::vector<int> host_block_first_cols(const std::vector<double>& M, size_t ld, int nblk);
-// border_begin_row >= 0: the bordered envelope of the matrix itself (cholesky_envelope_bordered), rows from there on being the border
-static int cholesky_solve_impl(int n, const double* A, const double* b, double* x, double* L, int group, const int* last, int automatic_plan, int border_begin_row) {
   SK_GUARD_BEGIN
   if (n <= 0 || !A || !b || !x) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
-  if (sk_device_count() <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return SK_ERR_NO_DEVICE; }
-  if (group <= 0) group = automatic_plan ? 1 : 3;
-  const int rhs_row = n, npad = ((n + 1 + 127) / 128) * 128, nblk = npad / 128;
-  if (last) {
-    for (int c = 0; c < nblk; ++c) {
-      const bool ok = last[c] >= std::min(c, nblk - 2) && last[c] <= nblk - 1 && (c == 0 || last[c] >= last[c - 1]);
-      if (!ok) { set_error("invalid block envelope at block column %d", c); return SK_ERR_INVALID_ARGUMENT; }
-    }
-  }
-  std::vector<double> S((size_t)npad * npad, 0.0);
-  for (int i = 0; i < n; ++i) std::memcpy(&S[(size_t)i * npad], A + (size_t)i * n, (size_t)(i + 1) * sizeof(double));
-  std::memcpy(&S[(size_t)rhs_row * npad], b, (size_t)n * sizeof(double));
-  S[(size_t)rhs_row * npad + rhs_row] = 1e300;
-  for (int j = n + 1; j < npad; ++j) S[(size_t)j * npad + j] = 1.0;
-  std::vector<int> b_last, b_tail;
-  const int* tail = nullptr;
-  if (border_begin_row >= 0) {
-    cholesky_envelope_bordered(host_block_first_cols(S, (size_t)npad, nblk), border_begin_row / 128, &b_last, &b_tail);
-    last = b_last.data(); tail = b_tail.data();
-  }
-  DevBuf<double> dS, dLinv, dy; DevBuf<int> dinfo;
-  hipStream_t s = nullptr;
-  SK_HIP_TRY(dS.upload(S, s)); SK_HIP_TRY(dLinv.alloc((size_t)npad * 128)); SK_HIP_TRY(dLinv.zero(s));
-  DevBuf<double> dw;
-  SK_HIP_TRY(dy.alloc(npad)); SK_HIP_TRY(dw.alloc(npad)); SK_HIP_TRY(dinfo.alloc(1)); SK_HIP_TRY(dinfo.zero(s));
-  SK_HIP_TRY(cholesky_init());
-  CholeskyContext ctx;  // exercise the look-ahead path the solver uses
-  const bool la = ctx.init() == hipSuccess;
-  if (!la) (void)hipGetLastError();
-  SK_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  SK_HIP_TRY(hipDeviceSynchronize());  // uploads above ran on the null stream
-  const bool chain = automatic_plan != 0 && la && ctx.server != nullptr;  // (the plan; resident or not is the device's state)
-  cholesky_factor(dS.p, npad, npad, dLinv.p, dinfo.p, group, s, la ? &ctx : nullptr, nullptr, last, chain, -1, 1, nullptr, tail);
-  cholesky_backsolve(dS.p, npad, n, npad, rhs_row, dLinv.p, dw.p, dy.p, s, nullptr, last, dinfo.p, tail);
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  SK_HIP_TRY(hipStreamDestroy(s));
-  s = nullptr;
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  int info = 0;
-  SK_HIP_TRY(hipMemcpy(&info, dinfo.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (info == 2) { (void)cholesky_note_info(&ctx, info); set_error("the resident panel chain timed out"); return SK_ERR_HIP; }
-  if (info) { set_error("matrix is not positive definite"); return SK_ERR_EVALUATION_FAILED; }
-  std::vector<double> y(npad);
-  SK_HIP_TRY(hipMemcpy(y.data(), dy.p, npad * sizeof(double), hipMemcpyDeviceToHost));
-  std::memcpy(x, y.data(), (size_t)n * sizeof(double));
-  if (L) {
-    SK_HIP_TRY(hipMemcpy(S.data(), dS.p, S.size() * sizeof(double), hipMemcpyDeviceToHost));
-    for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) L[(size_t)i * n + j] = j <= i ? S[(size_t)i * npad + j] : 0.0;
-  }
-  return SK_OK;
+  return cholesky_solve_single(n, A, b, x, L, group, last, automatic_plan, -1);
   SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
-
-// Block envelope of a front held on the host (lower triangle, row-major, ld): first non-zero block column per block row.
-static std::vector<int> host_block_first_cols(const std::vector<double>& M, size_t ld, int nblk) {
-  std::vector<int> first_col(nblk);
-  for (int i = 0; i < nblk; ++i) {
-    first_col[i] = i;
-    for (int j = 0; j < i && first_col[i] == i; ++j) {
-      bool nz = false;
-      for (int r = 0; r < 128 && !nz; ++r) {
-        const double* row = &M[((size_t)i * 128 + r) * ld + (size_t)j * 128];
-        for (int c = 0; c < 128; ++c) if (row[c] != 0.0) { nz = true; break; }
-      }
-      if (nz) first_col[i] = j;
-    }
-  }
-  return first_col;
+int sk_cholesky_solve_bordered(int n, const double* A, const double* b, double* x, double* L, int group, int border_begin_row, int automatic_plan) {
+  SK_GUARD_BEGIN
+  if (n <= 0 || !A || !b || !x || border_begin_row < 0 || border_begin_row > n) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return cholesky_solve_single(n, A, b, x, L, group, nullptr, automatic_plan, border_begin_row);
+  SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
-static std::vector<int> host_block_envelope(const std::vector<double>& M, size_t ld, int nblk, int tail_rows = 1) {
-  return cholesky_envelope_last(host_block_first_cols(M, ld, nblk), tail_rows);
-}
-
 int sk_cholesky_solve_dissected(int n, const double* A, const double* b, double* x, int head, int tail_begin, int group, int automatic_plan) {
   SK_GUARD_BEGIN
   if (n <= 0 || !A || !b || !x || head < 0 || tail_begin < head || tail_begin > n) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
-  if (sk_device_count() <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return SK_ERR_NO_DEVICE; }
-  const int ra = head, rb = tail_begin, nt = n - rb, msep = rb - ra;
-  for (int i = rb; i < n; ++i)
-    for (int j = 0; j < ra; ++j)
-      if (A[(size_t)i * n + j] != 0.0) { set_error("the tail couples with the head at (%d, %d): not a separator", i, j); return SK_ERR_INVALID_ARGUMENT; }
-  if (group <= 0) group = automatic_plan ? 1 : 3;
-  const int nA = (ra + 127) / 128, nB = (nt + 127) / 128, E = (msep + 1 + 127) / 128;
-  const size_t dA = (size_t)(nA + E) * 128, dB = (size_t)(nB + E) * 128, dR = (size_t)E * 128;
-  std::vector<double> FA(dA * dA, 0.0), FB(dB * dB, 0.0), FR(dR * dR, 0.0);
-  // head: interior in order, border = separator in order, then the right-hand side
-  for (int i = 0; i < ra; ++i) std::memcpy(&FA[(size_t)i * dA], A + (size_t)i * n, (size_t)(i + 1) * sizeof(double));
-  for (int i = ra; i < nA * 128; ++i) FA[(size_t)i * dA + i] = 1.0;
-  for (int k = 0; k < msep; ++k) std::memcpy(&FA[((size_t)nA * 128 + k) * dA], A + (size_t)(ra + k) * n, (size_t)ra * sizeof(double));
-  std::memcpy(&FA[((size_t)nA * 128 + msep) * dA], b, (size_t)ra * sizeof(double));
-  // tail: interior in REVERSE order (t <-> global n - 1 - t), border = separator in reverse order, then the right-hand side
-  for (int t1 = 0; t1 < nt; ++t1)
-    for (int t2 = 0; t2 <= t1; ++t2) FB[(size_t)t1 * dB + t2] = A[(size_t)(n - 1 - t2) * n + (n - 1 - t1)];
-  for (int i = nt; i < nB * 128; ++i) FB[(size_t)i * dB + i] = 1.0;
-  for (int k = 0; k < msep; ++k)
-    for (int t = 0; t < nt; ++t) FB[((size_t)nB * 128 + k) * dB + t] = A[(size_t)(n - 1 - t) * n + (ra + msep - 1 - k)];
-  for (int t = 0; t < nt; ++t) FB[((size_t)nB * 128 + msep) * dB + t] = b[n - 1 - t];
-  // root: the separator's own block and right-hand side
-  for (int i = 0; i < msep; ++i) std::memcpy(&FR[(size_t)i * dR], A + (size_t)(ra + i) * n + ra, (size_t)(i + 1) * sizeof(double));
-  std::memcpy(&FR[(size_t)msep * dR], b + ra, (size_t)msep * sizeof(double));
-  FR[(size_t)msep * dR + msep] = 1e300;
-  for (size_t j = (size_t)msep + 1; j < dR; ++j) FR[j * dR + j] = 1.0;
-  std::vector<int> mapB(dR, -1);
-  for (int k = 0; k < msep; ++k) mapB[k] = msep - 1 - k;
-  mapB[msep] = msep;
-  const std::vector<int> lastA = host_block_envelope(FA, dA, nA + E), lastB = host_block_envelope(FB, dB, nB + E);
-  DevBuf<double> dFA, dFB, dFR, dLinv, dw, dy; DevBuf<int> dinfo, dmap;
-  hipStream_t s = nullptr;
-  SK_HIP_TRY(dFA.upload(FA, s)); SK_HIP_TRY(dFB.upload(FB, s)); SK_HIP_TRY(dFR.upload(FR, s)); SK_HIP_TRY(dmap.upload(mapB, s));
-  SK_HIP_TRY(dLinv.alloc((size_t)(nA + nB + E) * 128 * 128)); SK_HIP_TRY(dLinv.zero(s));
-  SK_HIP_TRY(dw.alloc(dA + dB + 2 * dR)); SK_HIP_TRY(dy.alloc(dA + dB + dR)); SK_HIP_TRY(dy.zero(s)); SK_HIP_TRY(dinfo.alloc(1)); SK_HIP_TRY(dinfo.zero(s));
-  SK_HIP_TRY(cholesky_init());
-  CholeskyContext ctx, ctxB;
-  const bool la = ctx.init() == hipSuccess;
-  if (!la) (void)hipGetLastError();
-  SK_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  SK_HIP_TRY(hipDeviceSynchronize());
-  if (la) cholesky_prepare(&ctx, s);  // the device's queue choice first: the second context takes the queues it leaves over
-  const bool side = la && ctxB.init_secondary(ctx) == hipSuccess;
-  if (la && !side) (void)hipGetLastError();
-  DissectedSystem d;
-  d.A.S = dFA.p; d.A.ld = (long)dA; d.A.nblk = nA + E; d.A.ncols = nA; d.A.last = lastA.data(); d.A.Linv = dLinv.p; d.A.rhs_row = nA * 128 + msep;
-  d.B.S = dFB.p; d.B.ld = (long)dB; d.B.nblk = nB + E; d.B.ncols = nB; d.B.last = lastB.data(); d.B.Linv = dLinv.p + (size_t)nA * 128 * 128; d.B.rhs_row = nB * 128 + msep;
-  d.R.S = dFR.p; d.R.ld = (long)dR; d.R.nblk = E; d.R.ncols = E; d.R.last = nullptr; d.R.Linv = dLinv.p + (size_t)(nA + nB) * 128 * 128; d.R.rhs_row = msep;
-  d.border_blocks = E; d.mapB = dmap.p;
-  const bool chain = automatic_plan != 0 && la && ctx.server != nullptr;
-  cholesky_dissected_factor(d, dinfo.p, group, s, la ? &ctx : nullptr, side ? &ctxB : nullptr, nullptr, nullptr, chain);
-  double *wA = dw.p, *wB = dw.p + dA, *wR = dw.p + dA + dB, *ybB = dw.p + dA + dB + dR;
-  double *yA = dy.p, *yB = dy.p + dA, *yR = dy.p + dA + dB;
-  cholesky_dissected_backsolve(d, msep, wR, yR, wA, yA, wB, yB, ybB, s, side ? &ctxB : nullptr, nullptr, dinfo.p);
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  SK_HIP_TRY(hipStreamDestroy(s));
-  int info = 0;
-  SK_HIP_TRY(hipMemcpy(&info, dinfo.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (info == 2) { (void)cholesky_note_info(&ctx, info); set_error("the resident panel chain timed out"); return SK_ERR_HIP; }
-  if (info) { set_error("matrix is not positive definite"); return SK_ERR_EVALUATION_FAILED; }
-  std::vector<double> y(dA + dB + dR);
-  SK_HIP_TRY(hipMemcpy(y.data(), dy.p, y.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (int i = 0; i < ra; ++i) x[i] = y[i];
-  for (int t = 0; t < nt; ++t) x[n - 1 - t] = y[dA + t];
-  for (int k = 0; k < msep; ++k) x[ra + k] = y[dA + dB + k];
-  return SK_OK;
+  return cholesky_solve_two_way(n, A, b, x, head, tail_begin, group, automatic_plan);
   SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
-
 int sk_cholesky_solve_segments(int n, const double* A, const double* b, double* x, int num_segments, const int* cuts, int group, int automatic_plan) {
   SK_GUARD_BEGIN
-  const int R = num_segments;
-  if (n <= 0 || !A || !b || !x || R < 2 || !cuts) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
-  if (sk_device_count() <= 0) { set_error("no HIP device available: libskeres_amd has no CPU fallback"); return SK_ERR_NO_DEVICE; }
-  // separator k (1 <= k < R) = rows [sb[k], se[k]); segment k = rows [se[k], sb[k + 1]) with se[0] = 0, sb[R] = n
-  std::vector<int> sb(R + 1, 0), se(R + 1, 0);
-  sb[R] = n;
-  for (int k = 1; k < R; ++k) { sb[k] = cuts[2 * (k - 1)]; se[k] = cuts[2 * (k - 1) + 1]; }
-  for (int k = 1; k <= R; ++k)
-    if (sb[k] < se[k - 1] || (k < R && (se[k] < sb[k] || se[k] > n))) { set_error("invalid cuts"); return SK_ERR_INVALID_ARGUMENT; }
-  for (int k = 1; k < R; ++k)
-    for (int i = se[k]; i < n; ++i)
-      for (int j = 0; j < sb[k]; ++j)
-        if (A[(size_t)i * n + j] != 0.0) { set_error("rows behind separator %d couple with rows before it at (%d, %d): not a separator", k, i, j); return SK_ERR_INVALID_ARGUMENT; }
-  if (group <= 0) group = automatic_plan ? 1 : 3;
-  auto a = [&](int i, int j) { return i >= j ? A[(size_t)i * n + j] : A[(size_t)j * n + i]; };  // (lower triangle given)
-  // root: every separator in order, then the right-hand side
-  std::vector<int> sep_off(R, 0);
-  for (int k = 1; k < R; ++k) sep_off[k] = sep_off[k - 1] + (se[k] - sb[k]);  // sep_off[k - 1]: offset of separator k; sep_off[R - 1]: total
-  const int nroot = sep_off[R - 1], E = (nroot + 1 + 127) / 128;
-  const size_t dR = (size_t)E * 128;
-  auto root_index = [&](int row) {  // global row of a separator -> root index
-    for (int k = 1; k < R; ++k) if (row >= sb[k] && row < se[k]) return sep_off[k - 1] + (row - sb[k]);
-    return -1;
-  };
-  std::vector<double> FR(dR * dR, 0.0);
-  for (int k = 1; k < R; ++k)
-    for (int i = sb[k]; i < se[k]; ++i) {
-      const int ri = root_index(i);
-      for (int k2 = 1; k2 <= k; ++k2)
-        for (int j = sb[k2]; j < se[k2] && j <= i; ++j) FR[(size_t)ri * dR + root_index(j)] = a(i, j);
-      FR[(size_t)nroot * dR + ri] = b[i];
-    }
-  FR[(size_t)nroot * dR + nroot] = 1e300;
-  for (size_t j = (size_t)nroot + 1; j < dR; ++j) FR[j * dR + j] = 1.0;
-  const std::vector<int> lastR = root_envelope(std::vector<int>(sep_off.begin(), sep_off.end()));
-  SK_HIP_TRY(cholesky_init());
-  CholeskyContext ctx;
-  const bool la = ctx.init() == hipSuccess;
-  if (!la) (void)hipGetLastError();
-  hipStream_t s = nullptr;
-  SK_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  if (la) cholesky_prepare(&ctx, s);
-  const bool chain = automatic_plan != 0 && la && ctx.server != nullptr;
-  DevBuf<double> dFR; DevBuf<int> dinfo;
-  SK_HIP_TRY(dFR.upload(FR, s)); SK_HIP_TRY(dinfo.alloc(1)); SK_HIP_TRY(dinfo.zero(s));
-  struct Leaf { SegmentLayout L; std::vector<int> order, map, last; DevBuf<double> F, Linv, w, y, yb; DevBuf<int> dmap; size_t dim; };
-  std::vector<std::unique_ptr<Leaf>> leaves;
-  for (int k = 0; k < R; ++k) {
-    std::unique_ptr<Leaf> lf(new Leaf());
-    const int lo = se[k], hi = sb[k + 1], ni = hi - lo;
-    const int left_n = k > 0 ? se[k] - sb[k] : 0, right_n = k + 1 < R ? se[k + 1] - sb[k + 1] : 0;
-    lf->L = segment_layout(ni, left_n, right_n);
-    const SegmentLayout& L = lf->L;
-    lf->dim = (size_t)L.nblk * 128;
-    const size_t d = lf->dim;
-    // front row -> global row (-1: padding / right-hand side)
-    lf->order.assign(d, -1);
-    for (int t = 0; t < ni; ++t) lf->order[t] = L.reversed ? hi - 1 - t : lo + t;
-    const int bo = L.ncols * 128;
-    if (L.right_off >= 0) for (int t = 0; t < right_n; ++t) lf->order[bo + L.right_off + t] = sb[k + 1] + t;
-    if (L.left_off >= 0) for (int t = 0; t < left_n; ++t) lf->order[bo + L.left_off + t] = L.reversed ? se[k] - 1 - t : sb[k] + t;
-    std::vector<double> F(d * d, 0.0);
-    for (size_t i = 0; i < d; ++i) {
-      const int gi = lf->order[i];
-      if (gi < 0) continue;
-      const bool border_i = (int)i >= bo;
-      for (size_t j = 0; j <= i && j < (size_t)ni; ++j) F[i * d + j] = a(gi, lf->order[j]);  // interior columns only: the border x border block starts at zero
-      (void)border_i;
-    }
-    for (int t = 0; t < ni; ++t) F[(size_t)L.rhs_row * d + t] = b[lf->order[t]];
-    for (int i = ni; i < bo; ++i) F[(size_t)i * d + i] = 1.0;
-    lf->last = host_block_envelope(F, d, L.nblk, L.tail_rows);
-    lf->map.assign(d - bo, -1);
-    for (size_t i = bo; i < d; ++i) if (lf->order[i] >= 0) lf->map[i - bo] = root_index(lf->order[i]);
-    lf->map[L.rhs_row - bo] = nroot;
-    SK_HIP_TRY(lf->F.upload(F, s)); SK_HIP_TRY(lf->dmap.upload(lf->map, s));
-    SK_HIP_TRY(lf->Linv.alloc((size_t)L.ncols * 128 * 128)); SK_HIP_TRY(lf->Linv.zero(s));
-    SK_HIP_TRY(lf->w.alloc(d)); SK_HIP_TRY(lf->y.alloc(d)); SK_HIP_TRY(lf->y.zero(s)); SK_HIP_TRY(lf->yb.alloc(d - bo));
-    if (ni > 0) {
-      cholesky_factor(lf->F.p, (long)d, (int)d, lf->Linv.p, dinfo.p, group, s, la ? &ctx : nullptr, nullptr, lf->last.data(), chain, L.ncols, L.tail_rows);
-      cholesky_border_add(dFR.p, (long)dR, lf->F.p, (long)d, L.ncols, L.nblk - L.ncols, lf->dmap.p, s);
-    }
-    SK_HIP_TRY(hipStreamSynchronize(s));  // (F, the host copy, goes out of scope)
-    leaves.push_back(std::move(lf));
-  }
-  DevBuf<double> dLinvR, dwR, dyR;
-  SK_HIP_TRY(dLinvR.alloc(dR * 128)); SK_HIP_TRY(dLinvR.zero(s)); SK_HIP_TRY(dwR.alloc(dR)); SK_HIP_TRY(dyR.alloc(dR));
-  cholesky_factor(dFR.p, (long)dR, (int)dR, dLinvR.p, dinfo.p, group, s, la ? &ctx : nullptr, nullptr, lastR.empty() ? nullptr : lastR.data(), chain);
-  cholesky_backsolve(dFR.p, (long)dR, nroot, (int)dR, nroot, dLinvR.p, dwR.p, dyR.p, s, nullptr, lastR.empty() ? nullptr : lastR.data(), dinfo.p);
-  std::vector<double> y(dR);
-  for (auto& lf : leaves) {
-    const SegmentLayout& L = lf->L;
-    if (L.ncols == 0) continue;
-    const int m = (L.nblk - L.ncols) * 128;
-    // border unknowns in the leaf's border order (zero in padding rows and in the right-hand-side row)
-    std::vector<int> gmap(lf->map);
-    gmap[L.rhs_row - L.ncols * 128] = -1;
-    DevBuf<int> dg;
-    SK_HIP_TRY(dg.upload(gmap, s));
-    cholesky_gather_map(dyR.p, dg.p, lf->yb.p, m, s);
-    cholesky_backsolve_front(lf->F.p, (long)lf->dim, L.nblk, L.ncols, L.rhs_row, lf->Linv.p, lf->yb.p, lf->w.p, lf->y.p, s, lf->last.data(), L.spike, L.tail_rows, dinfo.p);
-    SK_HIP_TRY(hipStreamSynchronize(s));
-  }
-  SK_HIP_TRY(hipStreamSynchronize(s));
-  int info = 0;
-  SK_HIP_TRY(hipMemcpy(&info, dinfo.p, sizeof(int), hipMemcpyDeviceToHost));
-  if (info == 2) { (void)cholesky_note_info(&ctx, info); (void)hipStreamDestroy(s); set_error("the resident panel chain timed out"); return SK_ERR_HIP; }
-  if (info) { (void)hipStreamDestroy(s); set_error("matrix is not positive definite"); return SK_ERR_EVALUATION_FAILED; }
-  SK_HIP_TRY(hipMemcpy(y.data(), dyR.p, dR * sizeof(double), hipMemcpyDeviceToHost));
-  for (int k = 1; k < R; ++k) for (int i = sb[k]; i < se[k]; ++i) x[i] = y[root_index(i)];
-  for (auto& lf : leaves) {
-    std::vector<double> yl(lf->dim);
-    SK_HIP_TRY(hipMemcpy(yl.data(), lf->y.p, lf->dim * sizeof(double), hipMemcpyDeviceToHost));
-    for (int t = 0; t < lf->L.ncols * 128; ++t) if (lf->order[t] >= 0) x[lf->order[t]] = yl[t];
-  }
-  SK_HIP_TRY(hipStreamDestroy(s));
-  return SK_OK;
+  if (n <= 0 || !A || !b || !x || num_segments < 2 || !cuts) { set_error("invalid argument"); return SK_ERR_INVALID_ARGUMENT; }
+  return cholesky_solve_multi_way(n, A, b, x, num_segments, cuts, group, automatic_plan);
   SK_GUARD_END(SK_ERR_INVALID_ARGUMENT)
 }
 

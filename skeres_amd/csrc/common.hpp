@@ -69,6 +69,12 @@ struct DevBuf {
   hipError_t zero(hipStream_t s) { return n ? hipMemsetAsync(p, 0, n * sizeof(T), s) : hipSuccess; }
 };
 
+// A stream of a call's own, destroyed on every way out of it.
+struct StreamGuard {
+  hipStream_t s = nullptr;
+  ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
+};
+
 // The loss nodes as a kernel takes them: a problem without any gets one trivial node, so that the pointer is never null.
 inline std::vector<LossNode> loss_nodes_or_trivial(std::vector<LossNode> nodes) {
   if (nodes.empty()) { LossNode t; t.type = kLossTrivial; t.f = t.g = -1; t.depth = 0; t.a = t.b = 0.0; nodes.push_back(t); }

@@ -11,11 +11,6 @@
 
 namespace sk {
 
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-};
-
 // device time between marks on the stream; off: mark() does nothing and every time is 0
 struct Marks {
   hipStream_t s = nullptr;

@@ -200,7 +200,13 @@ def test_compute_fails_loudly_without_a_device():
     assert np.array_equal(params.toArray(prob.num_parameters), prob.parameters)  # untouched: no silent CPU path
     with pytest.raises(sk.SkeresError, match="no HIP device"):
         sk.api.cholesky_solve(np.eye(4), np.ones(4))
-    cf = sk.BinaryScalarCost(1.0).toAutoDiffCostFunction()
+    with pytest.raises(sk.SkeresError, match="no HIP device"):
+        sk.api.cholesky_solve_bordered(np.eye(4), np.ones(4), 2)
+    with pytest.raises(sk.SkeresError, match="no HIP device"):
+        sk.api.cholesky_solve_dissected(np.eye(4), np.ones(4), 1, 2)
+    with pytest.raises(sk.SkeresError, match="no HIP device"):
+        sk.api.cholesky_solve_segments(np.eye(4), np.ones(4), [(1, 2)])
+    cf =sk.BinaryScalarCost(1.0).toAutoDiffCostFunction()
     with pytest.raises(sk.SkeresError, match="no HIP device"):
         cf.evaluate(sk.RichDoubleMatrix.ofSize(2, 2), sk.DoubleArray(1), None)
 
